@@ -8,11 +8,15 @@ P1 level/price search, packing, P2 placement, plan emission.  Inputs are
 uploaded to HBM before the timed region.  Each rank solves its own batch
 (replicas, no data-path collective; "scaling": "weak").
 
-    python bench.py                      # N=1, defaults finish in ~1 min
+    python bench.py                      # N=1: set up, warm up, time the steps, print the line
+    python bench.py --full               # + the legs, sub-records and the CPU baseline (~1 min)
+    python bench.py --dump-outputs DIR   # + the last timed step's outputs as DIR/<name>.npy
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N
 
-Printed on rank 0: ONE JSON line with metric/value/unit, roofline and
-cpu_baseline (DESIGN.md §6 defines every figure).
+Printed on rank 0: ONE JSON line with metric/value/unit/ms_per_step and the
+roofline of the timed steps; with --full also the on-chip figures, the
+host-boundary / single-instance / sustained legs, the C5 and C4 sub-records
+and cpu_baseline (DESIGN.md §6 defines every figure).
 """
 from __future__ import annotations
 
@@ -110,6 +114,13 @@ def parse():
     ap.add_argument("--jobs", type=int, default=900)
     ap.add_argument("--rounds", type=int, default=30)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline figure: the "
+                         "on-chip figures, the host-boundary / single-instance / sustained legs, the "
+                         "C5 and C4 sub-records and the CPU baseline (each still has its --no-* switch)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed (rank 0) as "
+                         "DIR/<name>.npy, float32 / float64 (see dump_outputs)")
     ap.add_argument("--cpu-baseline", dest="cpu_baseline", action="store_true", default=True)
     ap.add_argument("--no-cpu-baseline", dest="cpu_baseline", action="store_false")
     ap.add_argument("--workload", choices=("c3", "c4"), default="c3",
@@ -130,7 +141,40 @@ def parse():
                     help="profiling runs: skip the host-boundary / single-instance / sustained "
                          "legs and the C4 / C5 sub-records")
     ap.add_argument("--quiet", action="store_true")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_SEED = 20240  # the instance sample of dump_outputs
+DUMP_BYTES = 56_000_000  # per-job arrays of the sample (the per-instance scalars add 56 B each)
+
+
+def dump_outputs(path, results):
+    """--dump-outputs: what sw_batch_download returns for the last timed step.
+
+    The per-instance scalars (objective, utility, makespan, p2_objective,
+    bound as float64; iters, status as float64 whole numbers) are written for
+    every instance of the batch.  The per-job arrays are too large for that
+    at the default batch (32768 x 900 x 30 plan bytes), so plan [S, N, T] and
+    planned_rounds [S, N] (float32, 0/1 and whole numbers) hold a fixed
+    sample of S instances, drawn without replacement by a seeded generator
+    and listed in sample_instances (float64 indices into the batch); every
+    instance is kept while that fits DUMP_BYTES.  The inputs are seeded, so
+    two builds run with the same arguments write comparable files."""
+    os.makedirs(path, exist_ok=True)
+    n = len(results)
+    for key in ("objective", "utility", "makespan", "p2_objective", "bound", "iters", "status"):
+        np.save(os.path.join(path, key + ".npy"), np.array([r[key] for r in results], dtype=np.float64))
+    per = max(1, max(4 * r["plan"].size + 4 * r["planned_rounds"].size for r in results))
+    s = max(1, min(n, DUMP_BYTES // per))
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=s, replace=False))
+    np.save(os.path.join(path, "sample_instances.npy"), pick.astype(np.float64))
+    np.save(os.path.join(path, "plan.npy"),
+            np.stack([results[i]["plan"] for i in pick]).astype(np.float32))
+    np.save(os.path.join(path, "planned_rounds.npy"),
+            np.stack([results[i]["planned_rounds"] for i in pick]).astype(np.float32))
 
 
 CPU_SEEDS = (0, 1, 2)  # fixed C3 seeds of the CPU leg (sw_synth seeds 10000+)
@@ -265,17 +309,21 @@ def main_c4(args, world, rank, local, dist):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     barrier()
+    if args.dump_outputs and rank == 0:  # this rank's rows of the plan, the global scalars
+        dump_outputs(args.dump_outputs, [dict(r, plan=shard.plan.cpu().numpy(),
+                                              planned_rounds=shard.planned.cpu().numpy())])
     # the host-buffer boundary (sw_dist_plan_solve: per-job arrays up and the
-    # plan down over PCIe every solve), reported beside the value
-    hsteps = max(1, args.steps // 2)
-    barrier()
-    t1 = time.perf_counter()
-    for _ in range(hsteps):
-        rh = solver.dist_solve(local_arrays, lo, a.N)
-    torch.cuda.synchronize()
-    host_elapsed = time.perf_counter() - t1
-    barrier()
-    assert rh["objective"] == r["objective"] and rh["iters"] == r["iters"]
+    # plan down over PCIe every solve), reported beside the value (--full)
+    hsteps, host_elapsed = max(1, args.steps // 2), 0.0
+    if args.full:
+        barrier()
+        t1 = time.perf_counter()
+        for _ in range(hsteps):
+            rh = solver.dist_solve(local_arrays, lo, a.N)
+        torch.cuda.synchronize()
+        host_elapsed = time.perf_counter() - t1
+        barrier()
+        assert rh["objective"] == r["objective"] and rh["iters"] == r["iters"]
     if dist is not None:
         t = torch.tensor([elapsed, host_elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -300,8 +348,9 @@ def main_c4(args, world, rank, local, dist):
             "collective_steps": r["iters"],
             "transport": args.transport,
             "objective": r["objective"],
-            "host_boundary_solves_per_s": hsteps / host_elapsed,
         }
+        if args.full:
+            line["host_boundary_solves_per_s"] = hsteps / host_elapsed
         emit(line)
     solver.close()
     if dist is not None:
@@ -346,8 +395,6 @@ def main():
 
     for _ in range(args.warmup):
         solver.run()
-    results = solver.download()
-    iters = np.array([r["iters"] for r in results], dtype=np.float64)
 
     solver.set_timing(True)
     barrier()
@@ -378,11 +425,19 @@ def main():
     avg_kernel_s = avg_plan_s + avg_p2x_s
     alg_bytes = float(args.batch * algorithmic_bytes(args.jobs, args.rounds))
     achieved = alg_bytes / avg_kernel_s if avg_kernel_s > 0 else 0.0
-    onchip = float(np.sum(iters) * pass_bytes(args.jobs, args.rounds))
     traffic = pmc_traffic(args.batch, args.jobs, args.rounds)
 
+    # the last timed step's results come to the host only for --dump-outputs
+    # and for the --full figures that read them
+    results = iters = None
+    if rank == 0 and (args.full or args.dump_outputs):
+        results = solver.download()
+        iters = np.array([r["iters"] for r in results], dtype=np.float64)
+    if results is not None and args.dump_outputs:
+        dump_outputs(args.dump_outputs, results)
+    legs = args.full and not args.no_legs
     extra = {}
-    if rank == 0 and not args.no_legs:
+    if rank == 0 and legs:
         extra = boundary_legs(args, solver, batch, results, local)
     solver.close()
     cpu = None
@@ -432,23 +487,25 @@ def main():
                          "reference line, not the bound: the working sets stay in VGPRs/LDS "
                          "(see limiter, onchip and cycles_per_instance)"),
             },
-            "onchip": {
+            "cycles_per_instance": cyc,
+            "cycles_note": (f"avg solve-kernel time x {CLOCK_HZ / 1e9:g} GHz x {NUM_CU} CUs / instances: "
+                            "CU-cycles one solve occupies"),
+        }
+        if args.full:  # the passes each instance took come from its downloaded result
+            onchip = float(np.sum(iters) * pass_bytes(args.jobs, args.rounds))
+            line["onchip"] = {
                 "bytes_per_pass": pass_bytes(args.jobs, args.rounds),
                 "passes_per_instance": float(np.mean(iters)),
                 "bytes_per_s": onchip / avg_kernel_s if avg_kernel_s > 0 else 0.0,
                 "what": "key rows + per-job state re-read from VGPR/LDS by every search / pack pass",
-            },
-            "cycles_per_instance": cyc,
-            "cycles_note": (f"avg solve-kernel time x {CLOCK_HZ / 1e9:g} GHz x {NUM_CU} CUs / instances: "
-                            "CU-cycles one solve occupies"),
-            "cpu_baseline": cpu,
-        }
+            }
+            line["cpu_baseline"] = cpu
         line.update(extra)
-    if not (args.no_c5 or args.no_legs):
+    if legs and not args.no_c5:
         c5 = guarded(c5_leg, "c5_sweep", args, world, rank, local, dist, line)
         if line is not None:
             line["c5_sweep"] = c5
-    if not (args.no_c4 or args.no_legs):
+    if legs and not args.no_c4:
         c4 = guarded(c4_leg, "c4_sharded", args, world, rank, local, dist, line)
         if line is not None:
             line["c4_sharded"] = c4
@@ -458,7 +515,7 @@ def main():
                 line["c4_sharded_peer"] = c4p
     # the CPU leg runs last: the host-synchronised C4 controller timed after
     # 15 s of HiGHS on the same core came out 0.25 ms slower per solve
-    if rank == 0 and args.cpu_baseline:
+    if rank == 0 and args.full and args.cpu_baseline:
         try:
             cpu = cpu_baseline(args)
         except Exception as e:  # reported, never silently substituted

@@ -13,7 +13,7 @@ export TMPDIR=/tmp
 B=32768
 timeout -k 10 400 python -u -m pytest tests -m gpu -x -v --timeout 200 --timeout-method thread > $OUT/pytest_gpu.log 2>&1 &&
 timeout -k 10 180 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 &&
-timeout -k 10 300 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err &&
+timeout -k 10 300 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err &&
 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_c3 -o run -- python3 bench.py --no-cpu-baseline --no-legs --steps 5 --warmup 1 > $OUT/prof_c3.json 2> $OUT/prof_c3.err &&
 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_c4 -o run -- python3 bench.py --workload c4 --steps 20 --warmup 2 > $OUT/prof_c4.json 2> $OUT/prof_c4.err &&
 bash tools/pmc_c3.sh $TAG/pmc $B &&

@@ -10,5 +10,5 @@ timeout -k 10 600 python -u -m pytest -x -v --timeout 300 --timeout-method threa
   tests/test_frag_fuzz.py tests/test_gpu_parity.py tests/test_gpu_shard.py tests/test_gpu_p2.py tests/test_gpu_fuzz.py \
   tests/test_gpu_sim.py tests/test_oracle_c3.py > $OUT/pytest.log 2>&1 || { tail -40 $OUT/pytest.log; exit 1; }
 tail -3 $OUT/pytest.log
-timeout -k 10 300 python -u bench.py --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err || exit 1
+timeout -k 10 300 python -u bench.py --full --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err || exit 1
 python3 -c "import json;b=json.load(open('$OUT/bench.json'));print(b['value'],b['single_instance_ms'],b['c5_sweep']['value'],b['c4_sharded']['ms_per_solve'])"
