@@ -53,6 +53,23 @@ static int split_min_count() {
     return v;
 }
 
+/* Split batches of at least this many instances run the pack stage as three
+ * kernels — sort, round loops one wave per instance, place (sw_launch_split
+ * with loop_split; SW_LOOP_MIN overrides) — instead of sw_pack_kernel.  The
+ * loop kernel pays where the batch fills the chip several times over, so
+ * that a CU holds tens of loop chains at once; a small split batch ends with
+ * its slowest instance's own chain, which two more launches only lengthen
+ * (DESIGN.md §7.1).  Interleaved against sw_pack_kernel on C3 instances
+ * (profiles/r19_loop_batch_sweep.jsonl): 512 (the C5 sweep) −2 %, 2,048
+ * −1.5 %, 4,096 +5.2 %, 8,192 (a host-boundary chunk) +7.5 %, 32,768 +8.7 %
+ * — so from 4,096. */
+static int loop_min_count() {
+    static const int v = [] {
+        const char* e = getenv("SW_LOOP_MIN");
+        return e ? atoi(e) : 4096;
+    }();
+    return v;
+}
 
 extern "C" size_t sw_plan_kernel_lds_bytes(int one);
 extern "C" hipError_t sw_launch_plan(const sw_batch_dev* B, int KT, int one, size_t lds,
@@ -191,6 +208,7 @@ sw_handle* sw_create(const sw_config* cfg) {
         if (h->d_in.reserve(in_block_bytes((int32_t)I, (int64_t)J)) ||
             h->d_res.reserve(res_block_bytes((int32_t)I, (int64_t)J, (int64_t)J * SW_MAX_ROUNDS)) ||
             h->d_masks.reserve(J) || h->d_nb.reserve(J) || h->d_lvl.reserve(I) ||
+            h->d_lws.reserve(J) || h->d_lwm.reserve(J) || h->d_lwa.reserve(I) ||
             h->d_p2ws.reserve(J * SW_P2X_ARR_BYTES) ||
             h->h_in.reserve(in_block_bytes((int32_t)I, (int64_t)J)) ||
             h->h_res.reserve(res_block_bytes((int32_t)I, (int64_t)J, (int64_t)J * SW_MAX_ROUNDS)) ||
@@ -215,6 +233,7 @@ void sw_destroy(sw_handle* h) {
     h->d_ws_u8.release(); h->d_ws_u64.release(); h->d_ws_sort.release();
     h->d_ws_keys.release(); h->d_ws_jc.release(); h->d_stamps.release();
     h->d_masks.release(); h->d_p2ws.release(); h->d_nb.release(); h->d_lvl.release();
+    h->d_lws.release(); h->d_lwm.release(); h->d_lwa.release();
     h->h_in.release(); h->h_res.release();
     h->h_masks.release();
     for (hipEvent_t ev : h->ev_chunk)
@@ -323,7 +342,8 @@ int prepare_batch(sw_handle* h, int32_t count, const sw_problem* probs) {
     const size_t Jz = (size_t)std::max<int64_t>(J, 1);
     const size_t inb = in_block_bytes(std::max(count, 1), (int64_t)Jz), resb = res_block_bytes(std::max(count, 1), (int64_t)Jz, std::max<int64_t>(P, 1));
     if (h->d_in.reserve(inb) || h->d_res.reserve(resb) ||
-        h->d_masks.reserve(Jz) || h->d_nb.reserve(Jz) || h->d_lvl.reserve(std::max(count, 1)))
+        h->d_masks.reserve(Jz) || h->d_nb.reserve(Jz) || h->d_lvl.reserve(std::max(count, 1)) ||
+        h->d_lws.reserve(Jz) || h->d_lwm.reserve(Jz) || h->d_lwa.reserve(std::max(count, 1)))
         return fail(h, SW_ERR_HIP, "device allocation failed");
     if (maxN > SW_LDS_JOBS || maxT > 32) {
         const int KT = maxT <= 32 ? 32 : 64;
@@ -472,6 +492,9 @@ int launch(sw_handle* h, int32_t lo, int32_t hi, hipStream_t s, bool timed, bool
     B.out = h->d_out + lo;
     B.nb = h->d_nb.p;
     B.lvl = h->d_lvl.p + lo;
+    B.lws = h->d_lws.p;
+    B.lwm = h->d_lwm.p;
+    B.lwa = h->d_lwa.p + lo;
 #ifdef SW_STAMPS
     B.stamps = h->d_stamps.p + (size_t)lo * SW_STAMP_SLOTS;
 #endif
@@ -494,7 +517,9 @@ int launch(sw_handle* h, int32_t lo, int32_t hi, hipStream_t s, bool timed, bool
      * kernel — each instance's P2 exchange step runs at its end, in the same
      * workgroup — then the full kernel for the instances the pack kernel
      * marked, with their exchange steps fused at its end too
-     * (sw_launch_split).  Smaller on-chip batches of at most fuse_max_count()
+     * (sw_launch_split); from loop_min_count() instances the pack kernel is
+     * three — sort, round loops one wave per instance, place — inside the
+     * same plan timing events.  Smaller on-chip batches of at most fuse_max_count()
      * instances: the full kernel with the exchange fused at its end.  The
      * rest (larger on-chip batches below the split size, and every batch with
      * an instance above SW_LDS_JOBS jobs or 32 rounds): the full kernel, then
@@ -508,6 +533,7 @@ int launch(sw_handle* h, int32_t lo, int32_t hi, hipStream_t s, bool timed, bool
     const bool split = one && (force_split >= 0 ? force_split != 0 : B.count > split_min_count());
 #endif
     B.fuse_p2x = one && (split || B.count <= fuse_max_count()); /* split: always fused */
+    B.loop_split = split && B.count >= loop_min_count();
     if (B.fuse_p2x) lds = std::max(lds, sw_p2x_kernel_lds_bytes(h->maxN, h->maxT));
     hipError_t e = split ? sw_launch_split(&B, sw_p2x_kernel_lds_bytes(h->maxN, h->maxT), s)
                          : sw_launch_plan(&B, B.KT, one, lds, s);
@@ -684,11 +710,17 @@ int run_streams(const sw_handle* h) {
 }
 
 int launch_streams(sw_handle* h, int ns) {
-    if (h->xs.empty()) {
-        h->xs.assign(kMaxRunStreams - 1, nullptr);
-        h->ev_xs.assign(kMaxRunStreams, nullptr);
-        for (auto& x : h->xs) SW_HIP(h, hipStreamCreateWithFlags(&x, hipStreamNonBlocking));
-        for (auto& ev : h->ev_xs) SW_HIP(h, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    /* only the ns − 1 extra streams in use: with few hardware queues an idle
+     * stream more can put a chunk's stream on a queue the copy streams share */
+    while ((int)h->xs.size() < ns - 1) {
+        hipStream_t x = nullptr;
+        SW_HIP(h, hipStreamCreateWithFlags(&x, hipStreamNonBlocking));
+        h->xs.push_back(x);
+    }
+    while ((int)h->ev_xs.size() < ns) {
+        hipEvent_t ev = nullptr;
+        SW_HIP(h, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        h->ev_xs.push_back(ev);
     }
     const bool timed = h->timing;
     if (timed) {

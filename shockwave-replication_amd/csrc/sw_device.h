@@ -82,5 +82,12 @@ struct sw_batch_dev {
     int32_t fuse_p2x;    /* sw_plan_kernel: run the exchange step after the solve (sw_p2x_inst.h) */
     int32_t want_masks;  /* sw_pack_kernel: store the final masks (a caller asked for plan_masks) */
     int32_t lds_bytes;   /* sw_pack_kernel: its dynamic LDS allocation (the exchange arrays' room) */
+    int32_t loop_split;  /* sw_launch_split: the pack stage as sort / rounds / place kernels (0: sw_pack_kernel) */
+    /* their workspace, indexed like nb (position p of an instance at job_off + p,
+     * p < A ≤ N): position words r | w << 8 | job << 16, round masks; and the
+     * positions per instance (−1: marked for sw_plan_kernel) */
+    uint32_t* lws;
+    uint64_t* lwm;
+    int32_t* lwa;
     uint64_t* stamps; /* diagnostic builds only (SW_STAMPS): [count][SW_STAMP_SLOTS] cycles (8…13: pack round-loop phases, 16…: level search, 32…: exchange) */
 };

@@ -90,6 +90,11 @@ struct sw_handle {
     DevBuf<uint64_t> d_masks;     /* final round masks (plan kernel → P2 exchange) */
     DevBuf<uint8_t> d_nb;         /* level-search counts (level kernel → pack kernel) */
     DevBuf<sw_lvl_dev> d_lvl;     /* level-search results per instance                */
+    /* the loop workspace of the three-kernel pack stage (sw_device.h lws / lwm /
+     * lwa): position words and round masks per job slot, positions per instance */
+    DevBuf<uint32_t> d_lws;
+    DevBuf<uint64_t> d_lwm;
+    DevBuf<int32_t> d_lwa;
     DevBuf<unsigned char> d_p2ws; /* P2 exchange arrays of instances > SW_LDS_JOBS jobs */
     DevBuf<uint64_t> d_stamps; /* SW_STAMPS diagnostic builds */
     /* pinned staging */

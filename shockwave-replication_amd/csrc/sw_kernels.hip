@@ -164,6 +164,7 @@ struct Ctx {
     uint64_t* lsp; /* level-search stamps */
     uint64_t ls_t;
     uint64_t lsa[9];
+    uint64_t pk0_, srt0; /* pack sub-phase stamps (PK_STAMP) */
 #endif
     /* per-job state (LDS when ONE, HBM workspace otherwise) */
     uint8_t *ncur, *lcur, *tkcur, *nbest, *placed, *placed2, *nfin;
@@ -1060,14 +1061,10 @@ struct Ctx {
      * every other job's row and count untouched.
      * Writes y[job] (round bitmask) and placed_out[job].
      */
-    __device__ __forceinline__ void pack(int MODE, const uint8_t* nin, uint64_t* y,
-                                         uint8_t* placed_out) {
-        __syncthreads();
 #ifdef SW_STAMPS
-        /* pack sub-phases, thread 0's view: swp[40] keys and offsets, [41]
-         * compaction after the sort, [42] the round loop with its staging,
-         * [43] the row write-back (swp = stamps + 8: slots 48…51) */
-        uint64_t pk0_ = __builtin_amdgcn_s_memtime();
+    /* pack sub-phases, thread 0's view: swp[40] keys and offsets, [41]
+     * compaction after the sort, [42] the round loop with its staging,
+     * [43] the row write-back (swp = stamps + 8: slots 48…51) */
 #define PK_STAMP(k)                                                      \
     do {                                                                 \
         const uint64_t n_ = __builtin_amdgcn_s_memtime();                \
@@ -1079,113 +1076,159 @@ struct Ctx {
     do {            \
     } while (0)
 #endif
+
+    /*
+     * pack()'s front half: the order keys of pack<MODE> in khi / klo (one
+     * sort word in khi for the ratio orders), the rows y of the jobs it owns
+     * zeroed (ZY; a caller that zeroes them itself passes false) and the
+     * number of active jobs A_.  When the positions fit one per thread
+     * (SMALL, or A_ ≤ SW_BLOCK) it also compacts and sorts them and returns
+     * true with thread t's position: mine (t < A_), its job jp1 and packed
+     * state st1 (r | w << 8, 0 past A_); otherwise the keys are left for the
+     * 1024-slot sort.
+     */
+    template <bool ZY = true>
+    __device__ __forceinline__ bool pack_front(int MODE, const uint8_t* nin, uint64_t* y,
+                                               uint64_t (&khi)[SW_JPT], uint64_t (&klo)[SW_JPT], int& A_,
+                                               bool& mine, int& jp1, uint32_t& st1) {
+        constexpr int E = SW_JPT;
         double Mb = 0.0;
-        const int32_t* capsp = MODE == 5 ? caps : nullptr;
         if (MODE == 1 || MODE == 3) {
             for_jobs([&](int j, int s) { Mb = sw_max(Mb, gval(j, s, nin[j])); });
             Mb = blk.dmax(Mb);
         }
         int64_t act_l = 0;
+#pragma unroll
+        for (int s = 0; s < E; ++s) { khi[s] = 0; klo[s] = 0; }
+        for_jobs([&](int j, int s) {
+            key_of(MODE, nin, Mb, j, s, khi[s], klo[s]);
+            act_l += nin_of(MODE, nin, j) > 0;
+            if constexpr (ZY)
+                if (owns(MODE, nin, j)) y[j] = 0;
+        });
+        /* the active jobs' slots in job order (klo ≠ 0 exactly when the
+         * job brings rounds); the total is A */
+        int32_t A32;
+        const int32_t abase = blk.exscan((int32_t)act_l, A32);
+        A_ = A32;
+        PK_STAMP(0);
+#ifdef SW_STAMPS
+        const uint64_t srt0_ = __builtin_amdgcn_s_memtime();
+        srt0 = srt0_;
+#endif
+        /* the ratio orders (modes 2, 4, 5: k2 = 0) sort one 64-bit word
+         * per job, key << 11 | (2047 − job) (N ≤ SW_LDS_JOBS), exactly
+         * the order (k1 desc, job asc); the P1 orders 1 / 3 sort (k1, k2,
+         * job) as two words */
+        const bool ratio = MODE == 2 || MODE == 4 || MODE == 5;
+        if (ratio) {
+#pragma unroll
+            for (int s = 0; s < E; ++s)
+                khi[s] = khi[s] != 0 || klo[s] != 0
+                             ? (khi[s] << 11) | (uint64_t)(2047u - (0xFFFFFFFFu - (uint32_t)klo[s]))
+                             : 0ull;
+        }
+        if (!(SMALL || A_ <= SW_BLOCK)) return false;
+        /* at most one position per thread (a C3 instance places ~1/3
+         * of its jobs): compact the active keys through LDS, sort
+         * SW_BLOCK of them one per thread (half the network of the
+         * 1024-slot sort), and thread t owns position t, so every pass
+         * of the round loop walks one position instead of E */
+        /* the pack kernel (SMALL) sorts ratio orders only (modes 4
+         * and 5): one word per position, and its LDS holds
+         * 3·SW_BLOCK words here (four instances per CU) */
+        uint64_t* xh = sbuf;
+        uint64_t* xl = sbuf + SW_BLOCK;
+        int b = abase;
+#pragma unroll
+        for (int s = 0; s < E; ++s)
+            if (klo[s] != 0) {
+                xh[b] = khi[s];
+                if constexpr (!SMALL) xl[b] = klo[s];
+                ++b;
+            }
+        __syncthreads();
+        mine = (int)threadIdx.x < A_;
+        uint64_t h1 = mine ? xh[threadIdx.x] : 0ull;
+        uint64_t l1 = 0ull;
+        if constexpr (SMALL) {
+            sort_one<false>(h1, l1, sbuf + SW_BLOCK);
+        } else {
+            l1 = mine ? xl[threadIdx.x] : 0ull;
+            if (ratio) sort_one<false>(h1, l1, sbuf + 2 * SW_BLOCK);
+            else sort_one<true>(h1, l1, sbuf + 2 * SW_BLOCK);
+        }
+#ifdef SW_STAMPS
+        if (threadIdx.x == 0 && swp) swp[7] += __builtin_amdgcn_s_memtime() - srt0_;
+        pk0_ = __builtin_amdgcn_s_memtime();
+#endif
+        jp1 = !mine ? 0
+              : ratio ? (int)(2047u - (uint32_t)(h1 & 2047u))
+                      : (int)(0xFFFFFFFFu - (uint32_t)(l1 & 0xFFFFFFFFu));
+        const uint32_t wq = MODE == 5 ? 1u : (uint32_t)w_in[jp1];
+        st1 = mine ? ((uint32_t)nin[jp1] | (wq << 8)) : 0u;
+        PK_STAMP(1);
+        return true;
+    }
+
+    /* pack()'s loop for one position per thread: the round loop in wave 0
+     * (sw_pack_rounds_one; the sort is done with sbuf, whose first 6 KB stage
+     * the states): the pack kernel sizes it by A, the plan kernel takes the
+     * 6- or 8-position form (its register file has no room for four copies) */
+    __device__ __forceinline__ void pack_loop(int MODE, int A_, uint32_t& st1, uint64_t& mk1) {
+        const int32_t* capsp = MODE == 5 ? caps : nullptr;
+#ifdef SW_STAMPS
+        sw_pack_rounds_one<SMALL>(PL, A_, T, G, st1, mk1, sbuf, capsp, swp);
+#else
+        sw_pack_rounds_one<SMALL>(PL, A_, T, G, st1, mk1, sbuf, capsp);
+#endif
+        PK_STAMP(2);
+    }
+
+    /* pack()'s back half for one position per thread: the counts of the jobs
+     * pack<MODE> owns zeroed, then thread t's position — job jp1, residual
+     * state st1, round mask mk1 — scattered to y and placed_out (y's rows
+     * are zero since the front half) */
+    __device__ __forceinline__ void pack_back(int MODE, const uint8_t* nin, uint64_t* y,
+                                              uint8_t* placed_out, bool mine, int jp1, uint32_t st1,
+                                              uint64_t mk1) {
+        for_jobs([&](int j, int s) {
+            (void)s;
+            if (owns(MODE, nin, j)) placed_out[j] = 0;
+        });
+        __syncthreads();
+        if (mine) {
+            y[jp1] = mk1;
+            placed_out[jp1] = (uint8_t)(nin[jp1] - st_r(st1));
+        }
+        __syncthreads();
+        PK_STAMP(3);
+    }
+
+    __device__ __forceinline__ void pack(int MODE, const uint8_t* nin, uint64_t* y,
+                                         uint8_t* placed_out) {
+        __syncthreads();
+#ifdef SW_STAMPS
+        pk0_ = __builtin_amdgcn_s_memtime();
+#endif
+        const int32_t* capsp = MODE == 5 ? caps : nullptr;
         if constexpr (ONE) {
             constexpr int E = SW_JPT;
             uint64_t khi[E], klo[E];
-#pragma unroll
-            for (int s = 0; s < E; ++s) { khi[s] = 0; klo[s] = 0; }
-            for_jobs([&](int j, int s) {
-                key_of(MODE, nin, Mb, j, s, khi[s], klo[s]);
-                act_l += nin_of(MODE, nin, j) > 0;
-                if (owns(MODE, nin, j)) y[j] = 0;
-            });
-            /* the active jobs' slots in job order (klo ≠ 0 exactly when the
-             * job brings rounds); the total is A */
-            int32_t A32;
-            const int32_t abase = blk.exscan((int32_t)act_l, A32);
-            const int A_ = A32;
-            PK_STAMP(0);
-#ifdef SW_STAMPS
-            const uint64_t srt0_ = __builtin_amdgcn_s_memtime();
-#endif
-            /* the ratio orders (modes 2, 4, 5: k2 = 0) sort one 64-bit word
-             * per job, key << 11 | (2047 − job) (N ≤ SW_LDS_JOBS), exactly
-             * the order (k1 desc, job asc); the P1 orders 1 / 3 sort (k1, k2,
-             * job) as two words */
-            const bool ratio = MODE == 2 || MODE == 4 || MODE == 5;
-            if (ratio) {
-#pragma unroll
-                for (int s = 0; s < E; ++s)
-                    khi[s] = khi[s] != 0 || klo[s] != 0
-                                 ? (khi[s] << 11) | (uint64_t)(2047u - (0xFFFFFFFFu - (uint32_t)klo[s]))
-                                 : 0ull;
-            }
-            if (SMALL || A_ <= SW_BLOCK) {
-                /* at most one position per thread (a C3 instance places ~1/3
-                 * of its jobs): compact the active keys through LDS, sort
-                 * SW_BLOCK of them one per thread (half the network of the
-                 * 1024-slot sort), and thread t owns position t, so every pass
-                 * of the round loop walks one position instead of E */
-                /* the pack kernel (SMALL) sorts ratio orders only (modes 4
-                 * and 5): one word per position, and its LDS holds
-                 * 3·SW_BLOCK words here (four instances per CU) */
-                uint64_t* xh = sbuf;
-                uint64_t* xl = sbuf + SW_BLOCK;
-                int b = abase;
-#pragma unroll
-                for (int s = 0; s < E; ++s)
-                    if (klo[s] != 0) {
-                        xh[b] = khi[s];
-                        if constexpr (!SMALL) xl[b] = klo[s];
-                        ++b;
-                    }
-                __syncthreads();
-                const bool mine = (int)threadIdx.x < A_;
-                uint64_t h1 = mine ? xh[threadIdx.x] : 0ull;
-                uint64_t l1 = 0ull;
-                if constexpr (SMALL) {
-                    sort_one<false>(h1, l1, sbuf + SW_BLOCK);
-                } else {
-                    l1 = mine ? xl[threadIdx.x] : 0ull;
-                    if (ratio) sort_one<false>(h1, l1, sbuf + 2 * SW_BLOCK);
-                    else sort_one<true>(h1, l1, sbuf + 2 * SW_BLOCK);
-                }
-#ifdef SW_STAMPS
-                if (threadIdx.x == 0 && swp) swp[7] += __builtin_amdgcn_s_memtime() - srt0_;
-                pk0_ = __builtin_amdgcn_s_memtime();
-#endif
-                const int jp1 = !mine ? 0
-                                : ratio ? (int)(2047u - (uint32_t)(h1 & 2047u))
-                                        : (int)(0xFFFFFFFFu - (uint32_t)(l1 & 0xFFFFFFFFu));
-                const uint32_t wq = MODE == 5 ? 1u : (uint32_t)w_in[jp1];
-                uint32_t st1[1] = {mine ? ((uint32_t)nin[jp1] | (wq << 8)) : 0u};
-                uint64_t mk1[1] = {0ull};
-                PK_STAMP(1);
-                /* the round loop in wave 0 (sw_pack_rounds_one; the sort is
-                 * done with sbuf, whose first 6 KB stage the states): the
-                 * pack kernel sizes it by A, the plan kernel takes the 6-
-                 * or 8-position form (its register file has no room for
-                 * four copies) */
-#ifdef SW_STAMPS
-                sw_pack_rounds_one<SMALL>(PL, A_, T, G, st1[0], mk1[0], sbuf, capsp, swp);
-#else
-                sw_pack_rounds_one<SMALL>(PL, A_, T, G, st1[0], mk1[0], sbuf, capsp);
-#endif
-                PK_STAMP(2);
-                for_jobs([&](int j, int s) {
-                    (void)s;
-                    if (owns(MODE, nin, j)) placed_out[j] = 0;
-                });
-                __syncthreads();
-                if (mine) {
-                    y[jp1] = mk1[0];
-                    placed_out[jp1] = (uint8_t)(nin[jp1] - st_r(st1[0]));
-                }
-                __syncthreads();
-                PK_STAMP(3);
+            int A_, jp1 = 0;
+            bool mine = false;
+            uint32_t st1 = 0u;
+            if (pack_front(MODE, nin, y, khi, klo, A_, mine, jp1, st1)) {
+                uint64_t mk1 = 0ull;
+                pack_loop(MODE, A_, st1, mk1);
+                pack_back(MODE, nin, y, placed_out, mine, jp1, st1, mk1);
             } else {
                 if constexpr (!SMALL) {
+                const bool ratio = MODE == 2 || MODE == 4 || MODE == 5;
                 if (ratio) sort_regs64(khi);
                 else sort_regs(khi, klo);
 #ifdef SW_STAMPS
-                if (threadIdx.x == 0 && swp) swp[7] += __builtin_amdgcn_s_memtime() - srt0_;
+                if (threadIdx.x == 0 && swp) swp[7] += __builtin_amdgcn_s_memtime() - srt0;
 #endif
                 uint32_t st[E];
                 uint64_t mk[E];
@@ -1221,6 +1264,12 @@ struct Ctx {
                             }
             }
         } else {
+            double Mb = 0.0;
+            if (MODE == 1 || MODE == 3) {
+                for_jobs([&](int j, int s) { Mb = sw_max(Mb, gval(j, s, nin[j])); });
+                Mb = blk.dmax(Mb);
+            }
+            int64_t act_l = 0;
             int NPg = 1;
             while (NPg < N) NPg <<= 1;
             uint64_t* shi = sbuf;
@@ -1259,8 +1308,8 @@ struct Ctx {
             }
             __syncthreads();
         }
-#undef PK_STAMP
     }
+#undef PK_STAMP
 
     /*
      * twin: repair_pack — yd / pd are the density-order pack of nin that left
@@ -1556,12 +1605,46 @@ __host__ __device__ constexpr size_t sw_level_lds_bytes() {
            r16(sizeof(float) * SW_JPT * SW_SETUP_CH * SW_BLOCK) + SW_JOB_LDS_BYTES;
 }
 
-/* LDS of the pack kernel: pack and repair state, counts, masks, sort exchange. */
-__host__ __device__ constexpr size_t sw_pack_lds_bytes() {
+/* LDS of the pack kernel: pack and repair state, counts, masks, sort
+ * exchange — the carve-up as constexpr offsets, shared by sw_pack_kernel and
+ * sw_place_kernel (pack_instance) and checked against the exchange step's
+ * layout at compile time (pack_tail). */
+struct sw_pack_carve {
+    size_t X, PL, misc, rep, nbest, placed, placed2, ycur, y2, sbuf, end;
+};
+__host__ __device__ constexpr sw_pack_carve sw_pack_offsets() {
     auto r16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
     const size_t NJ = SW_LDS_JOBS;
-    return r16(sizeof(sw_xchg)) + r16(sizeof(sw_pack_lds)) + r16(sizeof(int64_t) * 8) +
-           r16(sizeof(sw_repair_t)) + 3 * r16(NJ) + 2 * r16(8 * NJ) + r16(8 * 3 * SW_BLOCK);
+    sw_pack_carve o{};
+    size_t off = 0;
+    o.X = off;       off += r16(sizeof(sw_xchg));
+    o.PL = off;      off += r16(sizeof(sw_pack_lds));
+    o.misc = off;    off += r16(sizeof(int64_t) * 8);
+    o.rep = off;     off += r16(sizeof(sw_repair_t));
+    o.nbest = off;   off += r16(NJ);
+    o.placed = off;  off += r16(NJ);
+    o.placed2 = off; off += r16(NJ);
+    o.ycur = off;    off += r16(8 * NJ);
+    o.y2 = off;      off += r16(8 * NJ);
+    o.sbuf = off;    off += r16(8 * 3 * SW_BLOCK); /* compaction + sort_one exchange */
+    o.end = off;
+    return o;
+}
+__host__ __device__ constexpr size_t sw_pack_lds_bytes() { return sw_pack_offsets().end; }
+
+/* LDS of the sort kernel (sw_sort_kernel): the front half's carve-outs only. */
+struct sw_sort_carve {
+    size_t X, nbest, sbuf, end;
+};
+__host__ __device__ constexpr sw_sort_carve sw_sort_offsets() {
+    auto r16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    sw_sort_carve o{};
+    size_t off = 0;
+    o.X = off;     off += r16(sizeof(sw_xchg));
+    o.nbest = off; off += r16((size_t)SW_LDS_JOBS);
+    o.sbuf = off;  off += r16(8 * 3 * SW_BLOCK);
+    o.end = off;
+    return o;
 }
 
 /*
@@ -1695,6 +1778,51 @@ __device__ __forceinline__ void emit_plan_bytes(uint8_t* plan, const uint64_t* y
     }
 }
 
+/* The scalar fields of an on-chip pack context (pack_instance, sw_sort_kernel);
+ * the LDS pointers start null, each kernel sets the carve-outs it has. */
+template <class CTX>
+__device__ __forceinline__ void pack_ctx_scalars(CTX& c, const sw_batch_dev& B, const sw_inst_dev* I) {
+    c.inst = I;
+    c.N = I->N;
+    c.T = I->T;
+    c.G = I->G;
+    c.nb = I->nb;
+    c.C = (int64_t)I->G * I->T;
+    c.k = I->k;
+    c.inv_delta = 1.0 / I->delta;
+    c.passes = 0;
+    c.q = (c.N + SW_BLOCK - 1) / SW_BLOCK;
+    c.w_in = B.w + I->job_off;
+    c.p_in = B.p + I->job_off;
+#ifdef SW_STAMPS
+    c.swp = nullptr;
+    c.lsp = nullptr;
+#endif
+    c.blk.par = 0;
+    c.beta = c.ell = c.slope = nullptr;
+    c.PL = nullptr;
+    c.H = c.SH = c.caps = nullptr;
+    c.pwc = 0;
+    c.misc = nullptr;
+    c.rep = nullptr;
+    c.nbest = c.placed = c.placed2 = nullptr;
+    c.ncur = c.lcur = c.tkcur = c.nfin = c.tiecur = nullptr;
+    c.bnb = nullptr;
+    c.ycur = c.y2 = c.ybest = nullptr;
+    c.sbuf = nullptr;
+    c.pst = nullptr;
+    c.pord = nullptr;
+    c.pmask = nullptr;
+    c.gkeys = nullptr;
+    c.gjc = nullptr;
+}
+
+/* The position word of the loop workspace (sw_batch_dev::lws): the packed
+ * state of sw_pack.h with the position's job above it — r | w << 8 |
+ * job << 16 (job < SW_LDS_JOBS ≤ 2^11). */
+static_assert(SW_LDS_JOBS <= (1 << 11), "the job index fits the position word");
+#define SW_LWA_MARKED (-1) /* sw_batch_dev::lwa of an instance left to sw_plan_kernel */
+
 /*
  * The pack kernel (on-chip instances): solve_instance's path after the level
  * search when the density order places the counts (with its width-profile
@@ -1707,73 +1835,61 @@ __device__ __forceinline__ void emit_plan_bytes(uint8_t* plan, const uint64_t* y
  * share a CU.
  */
 /* Returns the instance's final placement (the masks, in LDS) for the tail
- * below, or nullptr when the instance was left to sw_plan_kernel. */
+ * below, or nullptr when the instance was left to sw_plan_kernel.  WS: the
+ * density pack's front half and round loop ran in sw_sort_kernel and
+ * sw_rounds_kernel; its back half reads their workspace (sw_place_kernel). */
+template <bool WS>
 __device__ __forceinline__ const uint64_t* pack_instance(const sw_batch_dev& B, unsigned char* smem, int inst_) {
     const sw_inst_dev* I = &B.inst[inst_];
     Ctx<32, true, true> c;
-    c.inst = I;
-    c.N = I->N;
-    c.T = I->T;
-    c.G = I->G;
-    c.nb = I->nb;
-    c.C = (int64_t)I->G * I->T;
-    c.k = I->k;
-    c.inv_delta = 1.0 / I->delta;
+    pack_ctx_scalars(c, B, I);
     const sw_lvl_dev lv = B.lvl[inst_];
     c.passes = lv.passes;
-    c.q = (c.N + SW_BLOCK - 1) / SW_BLOCK;
     const int64_t jo = I->job_off;
-    c.w_in = B.w + jo;
-    c.p_in = B.p + jo;
-#ifdef SW_STAMPS
-    c.swp = nullptr;
-    c.lsp = nullptr;
-#endif
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        unsigned char* p = smem + off;
-        off += (bytes + 15) & ~(size_t)15;
-        return p;
-    };
-    c.blk.X = (sw_xchg*)carve(sizeof(sw_xchg));
-    c.blk.par = 0;
-    c.beta = c.ell = c.slope = nullptr;
-    c.PL = (sw_pack_lds*)carve(sizeof(sw_pack_lds));
+    constexpr sw_pack_carve O = sw_pack_offsets();
+    c.blk.X = (sw_xchg*)(smem + O.X);
+    c.PL = (sw_pack_lds*)(smem + O.PL);
     c.H = c.PL->H[0];
     c.SH = c.PL->SH[0];
     c.caps = c.PL->H[1];
-    c.pwc = 0;
-    c.misc = (int64_t*)carve(sizeof(int64_t) * 8);
-    c.rep = (sw_repair_t*)carve(sizeof(sw_repair_t));
-    const int NJ = SW_LDS_JOBS;
-    c.nbest = carve(NJ);
-    c.placed = carve(NJ);
-    c.placed2 = carve(NJ);
-    c.ncur = c.lcur = c.tkcur = c.nfin = c.tiecur = nullptr;
-    c.bnb = nullptr;
-    c.ycur = (uint64_t*)carve(sizeof(uint64_t) * NJ);
-    c.y2 = (uint64_t*)carve(sizeof(uint64_t) * NJ);
-    c.ybest = nullptr;
-    c.sbuf = (uint64_t*)carve(sizeof(uint64_t) * 3 * SW_BLOCK); /* compaction + sort_one exchange */
-    c.pst = nullptr;
-    c.pord = nullptr;
-    c.pmask = nullptr;
-    c.gkeys = nullptr;
-    c.gjc = nullptr;
-    if (off != sw_pack_lds_bytes()) __builtin_trap();
-    int64_t act_l = 0;
-    c.for_jobs([&](int j, int s) {
-        (void)s;
-        c.nbest[j] = B.nb[jo + j];
-        act_l += c.nbest[j] > 0;
-    });
+    c.misc = (int64_t*)(smem + O.misc);
+    c.rep = (sw_repair_t*)(smem + O.rep);
+    c.nbest = smem + O.nbest;
+    c.placed = smem + O.placed;
+    c.placed2 = smem + O.placed2;
+    c.ycur = (uint64_t*)(smem + O.ycur);
+    c.y2 = (uint64_t*)(smem + O.y2);
+    c.sbuf = (uint64_t*)(smem + O.sbuf);
     sw_out_dev* out = &B.out[inst_];
-    if (c.blk.sum(act_l) > SW_BLOCK) { /* more positions than threads: sw_plan_kernel */
-        if (threadIdx.x == 0) out->status = SW_STATUS_SLOW_MARK;
-        return nullptr;
+    if constexpr (!WS) {
+        int64_t act_l = 0;
+        c.for_jobs([&](int j, int s) {
+            (void)s;
+            c.nbest[j] = B.nb[jo + j];
+            act_l += c.nbest[j] > 0;
+        });
+        if (c.blk.sum(act_l) > SW_BLOCK) { /* more positions than threads: sw_plan_kernel */
+            if (threadIdx.x == 0) out->status = SW_STATUS_SLOW_MARK;
+            return nullptr;
+        }
+        /* twin_plan_solve's first pack: the density order (mode 4) */
+        c.pack(4, c.nbest, c.ycur, c.placed);
+    } else {
+        /* the same pack, its front half and loop already run: position t's
+         * word and round mask from the workspace into pack()'s back half
+         * (whose first barrier also publishes the counts and the zeroed rows) */
+        const int A_ = sw_u32(B.lwa[inst_]);
+        if (A_ == SW_LWA_MARKED) return nullptr; /* marked by sw_sort_kernel */
+        c.for_jobs([&](int j, int s) {
+            (void)s;
+            c.nbest[j] = B.nb[jo + j];
+            c.ycur[j] = 0;
+        });
+        const bool mine = (int)threadIdx.x < A_;
+        const uint32_t word = mine ? B.lws[jo + threadIdx.x] : 0u;
+        const uint64_t mk1 = mine ? B.lwm[jo + threadIdx.x] : 0ull;
+        c.pack_back(4, c.nbest, c.ycur, c.placed, mine, (int)(word >> 16), word & 0xFFFFu, mk1);
     }
-    /* twin_plan_solve's first pack: the density order (mode 4) */
-    c.pack(4, c.nbest, c.ycur, c.placed);
     int64_t def_l = 0;
     c.for_jobs([&](int j, int s) {
         (void)s;
@@ -1864,6 +1980,10 @@ __device__ __forceinline__ void pack_tail(const sw_batch_dev& B, const uint64_t*
     sw_p2x_lds* L = reinterpret_cast<sw_p2x_lds*>(smem);
     const size_t Lsz = (sizeof(sw_p2x_lds) + 15) & ~(size_t)15;
     unsigned char* var = smem + Lsz;
+    /* ym is the pack's ycur (pack_instance): the scan below writes the step's
+     * exchange words L->X while ym is still read */
+    static_assert(offsetof(sw_p2x_lds, X) + sizeof(sw_xchg) <= sw_pack_offsets().ycur,
+                  "the pack's masks lie past the exchange words of sw_p2x_lds");
     sw_blk blk;
     blk.X = &L->X;
     blk.par = 0;
@@ -2565,16 +2685,132 @@ __global__ __launch_bounds__(SW_BLOCK, 4) void sw_level_kernel(sw_batch_dev B) {
  * first and all the exchanges after them. */
 __global__ __launch_bounds__(SW_BLOCK, 8) void sw_pack_kernel(sw_batch_dev B) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sw_smem[];
-    const uint64_t* ym = pack_instance(B, sw_smem, blockIdx.x);
+    const uint64_t* ym = pack_instance<false>(B, sw_smem, blockIdx.x);
     if (ym) pack_tail(B, ym, sw_smem, blockIdx.x); /* uniform: marked instances return */
+}
+
+/*
+ * The pack stage as three kernels (sw_launch_split with B->loop_split; large
+ * batches, loop_min_count() in sw_api.hip).  In sw_pack_kernel the density
+ * pack's round loop is one wave's dependent chain while the workgroup's other
+ * seven waves wait at a barrier, four chains per CU; here the loop is a
+ * kernel of its own with one wave per instance, so a CU holds as many chains
+ * as its LDS and wave slots admit and they hide each other's latency.  The
+ * three run pack()'s own front, loop and back (Ctx::pack_front,
+ * sw_pack_rounds_wave, Ctx::pack_back): the same placement bit for bit.
+ *
+ * sw_sort_kernel: the mark for more than SW_BLOCK positions, then the front
+ * half of the density pack (mode 4) — position p's word (r | w << 8 |
+ * job << 16) to lws[job_off + p], p < A ≤ N, and A to lwa.
+ */
+__global__ __launch_bounds__(SW_BLOCK, 8) void sw_sort_kernel(sw_batch_dev B) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sw_smem[];
+    const int inst_ = blockIdx.x;
+    const sw_inst_dev* I = &B.inst[inst_];
+    Ctx<32, true, true> c;
+    pack_ctx_scalars(c, B, I);
+    const int64_t jo = I->job_off;
+    constexpr sw_sort_carve O = sw_sort_offsets();
+    c.blk.X = (sw_xchg*)(sw_smem + O.X);
+    c.nbest = sw_smem + O.nbest;
+    c.sbuf = (uint64_t*)(sw_smem + O.sbuf);
+    int64_t act_l = 0;
+    c.for_jobs([&](int j, int s) {
+        (void)s;
+        c.nbest[j] = B.nb[jo + j];
+        act_l += c.nbest[j] > 0;
+    });
+    if (c.blk.sum(act_l) > SW_BLOCK) { /* more positions than threads: sw_plan_kernel */
+        if (threadIdx.x == 0) {
+            B.out[inst_].status = SW_STATUS_SLOW_MARK;
+            B.lwa[inst_] = SW_LWA_MARKED;
+        }
+        return;
+    }
+    __syncthreads(); /* as pack() opens: the counts are in LDS */
+    uint64_t khi[SW_JPT], klo[SW_JPT];
+    int A_, jp1 = 0;
+    bool mine = false;
+    uint32_t st1 = 0u;
+    c.template pack_front<false>(4, c.nbest, nullptr, khi, klo, A_, mine, jp1, st1);
+    if (mine) B.lws[jo + threadIdx.x] = st1 | ((uint32_t)jp1 << 16);
+    if (threadIdx.x == 0) B.lwa[inst_] = A_;
+}
+
+/* LDS of one loop wave: the loop's histograms and its 512 round masks. */
+struct sw_rounds_lds {
+    sw_pack_lds L;
+    uint64_t mk[SW_BLOCK];
+};
+
+template <int E1>
+__device__ __forceinline__ void rounds_wave_ws(sw_rounds_lds* S, int A, int T, int G, uint32_t* ws,
+                                               uint64_t* wm) {
+    const int lane = lane_id();
+    uint32_t st[E1];
+#pragma unroll
+    for (int i = 0; i < E1; ++i) {
+        const int p = E1 * lane + i;
+        st[i] = p < A ? (ws[p] & 0xFFFFu) : 0u; /* 0 past A, as the staged states */
+    }
+    sw_pack_rounds_wave<E1>(&S->L, T, G, st, S->mk);
+    /* its closing wave_sync: the masks are in LDS */
+#pragma unroll
+    for (int i = 0; i < E1; ++i) {
+        const int p = E1 * lane + i;
+        if (p < A) {
+            ws[p] = (ws[p] & 0xFFFF0000u) | st[i]; /* the job kept, r what is left */
+            wm[p] = S->mk[p];
+        }
+    }
+}
+
+/*
+ * sw_rounds_kernel: the density pack's round loop, one wave per instance and
+ * SW_LOOP_WPB instances per workgroup (no workgroup barrier: the waves share
+ * nothing).  Position p = E1·lane + i as in sw_pack_rounds_one, E1 chosen
+ * from A the same way; the residual states go back into lws, the round masks
+ * to lwm.  Four waves per workgroup (one per SIMD) measured 2 % faster than
+ * one-wave workgroups (0.544 against 0.555 ms for 32,768 C3 instances); every
+ * wave here is a loop wave, so the fused kernel's s_setprio(3) around the
+ * loop has nothing to overtake and is left out (0.542 against 0.544 ms with
+ * it, inside the launches' 8 µs spread).  Its 25 KB of LDS admit six
+ * workgroups per CU, six waves per SIMD — the launch bound; 58 VGPRs.
+ */
+#define SW_LOOP_WPB 4
+__global__ __launch_bounds__(64 * SW_LOOP_WPB, 6) void sw_rounds_kernel(sw_batch_dev B) {
+    __shared__ __attribute__((aligned(16))) sw_rounds_lds S_[SW_LOOP_WPB];
+    const int inst_ = (int)blockIdx.x * SW_LOOP_WPB + wave_id();
+    if (inst_ >= B.count) return;
+    const int A = sw_u32(B.lwa[inst_]);
+    if (A <= 0) return; /* marked, or nothing to place */
+    const sw_inst_dev* I = &B.inst[inst_];
+    const int T = sw_u32(I->T), G = sw_u32(I->G);
+    uint32_t* ws = B.lws + I->job_off;
+    uint64_t* wm = B.lwm + I->job_off;
+    sw_rounds_lds* S = &S_[wave_id()];
+    if (A <= 128) rounds_wave_ws<2>(S, A, T, G, ws, wm);
+    else if (A <= 256) rounds_wave_ws<4>(S, A, T, G, ws, wm);
+    else if (A <= 384) rounds_wave_ws<6>(S, A, T, G, ws, wm);
+    else rounds_wave_ws<8>(S, A, T, G, ws, wm);
+}
+
+/* sw_place_kernel: sw_pack_kernel from after its density pack's loop — the
+ * pack's back half from the workspace, repair, emit, exchange step, plan
+ * bytes — in the same LDS carve-up. */
+__global__ __launch_bounds__(SW_BLOCK, 8) void sw_place_kernel(sw_batch_dev B) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sw_smem[];
+    const uint64_t* ym = pack_instance<true>(B, sw_smem, blockIdx.x);
+    if (ym) pack_tail(B, ym, sw_smem, blockIdx.x);
 }
 
 /* LDS bytes the kernel needs (solve_instance checks its carve-up against it). */
 extern "C" size_t sw_plan_kernel_lds_bytes(int one) { return sw_plan_lds_bytes(one != 0); }
 
 /* The split path for on-chip batches (every instance N ≤ SW_LDS_JOBS and
- * T ≤ 32): level search, then pack + emit, then the full kernel for the
- * instances the pack kernel marked (B->only_slow set by the caller). */
+ * T ≤ 32): level search, then pack + emit (sw_pack_kernel, or with
+ * B->loop_split its sort / rounds / place kernels), then the full kernel for
+ * the instances the pack stage marked (B->only_slow set by the caller). */
 /* Every instance's exchange step runs inside these launches: the pack
  * kernel's instances at its end, the marked ones at the end of the full
  * kernel (p2x_lds: the step's LDS for the batch's largest instance). */
@@ -2584,7 +2820,14 @@ extern "C" hipError_t sw_launch_split(sw_batch_dev* B, size_t p2x_lds, hipStream
     B->fuse_p2x = 1;
     hipLaunchKernelGGL((sw_level_kernel<32>), grid, block, sw_level_lds_bytes(), stream, *B);
     B->lds_bytes = (int32_t)std::max(sw_pack_lds_bytes(), p2x_lds);
-    hipLaunchKernelGGL(sw_pack_kernel, grid, block, (size_t)B->lds_bytes, stream, *B);
+    if (B->loop_split) {
+        hipLaunchKernelGGL(sw_sort_kernel, grid, block, sw_sort_offsets().end, stream, *B);
+        dim3 rgrid((B->count + SW_LOOP_WPB - 1) / SW_LOOP_WPB), rblock(64 * SW_LOOP_WPB);
+        hipLaunchKernelGGL(sw_rounds_kernel, rgrid, rblock, 0, stream, *B);
+        hipLaunchKernelGGL(sw_place_kernel, grid, block, (size_t)B->lds_bytes, stream, *B);
+    } else {
+        hipLaunchKernelGGL(sw_pack_kernel, grid, block, (size_t)B->lds_bytes, stream, *B);
+    }
     B->only_slow = 1;
     hipLaunchKernelGGL((sw_plan_kernel<32, true>), grid, block, std::max(sw_plan_lds_bytes(true), p2x_lds),
                        stream, *B);
