@@ -362,6 +362,44 @@ int sw_mmf_allocate_types(sw_handle* h, int32_t num_jobs, int32_t num_types, con
                           const int32_t* scale_factors, const double* coefficients, double* allocation,
                           double* level);
 
+/*
+ * The Gavel FinishTimeFairness (Themis) baseline's allocation program
+ * (policies/finish_time_fairness.py:55-140) for one worker type, or several
+ * with identical throughputs:
+ *     minimise  max_j (elapsed_j + full_time_j / x_j) / isolated_time_j
+ *     s.t.      Σ_j scale_factor_j·x_j ≤ num_workers,  0 ≤ x_j ≤ 1,
+ * full_time_j = steps remaining / throughput (≥ 0; 0 for a job with no steps
+ * left), elapsed_j = time since the job's start (≥ 0), isolated_time_j = its
+ * expected duration under the isolated policy (> 0).  allocation (num_jobs
+ * doubles) receives x_j: the unique optimum when capacity binds, otherwise
+ * the analytic centre of the optimal face under the barrier of
+ * sw_mmf_allocate; which point of that face the reference's ECOS returns is
+ * not pinned (ECOS is absent, and its cone form of inv_pos is not this
+ * barrier).  level (optional, 2 doubles) receives the optimal ratio ρ* and
+ * the capacity multiplier μ (0 when capacity binds).  Values that are not
+ * finite, full_time < 0, elapsed < 0, isolated_time ≤ 0, a scale factor
+ * outside [1, 255] or num_workers ≤ 0 are SW_ERR_INVALID.  Synchronous;
+ * num_jobs = 0 is a no-op (policy.flatten returns None).
+ */
+int sw_ftf_allocate(sw_handle* h, int32_t num_jobs, int32_t num_workers,
+                    const int32_t* scale_factors, const double* full_time,
+                    const double* elapsed, const double* isolated_time,
+                    double* allocation, double* level);
+
+/*
+ * count independent instances of sw_ftf_allocate in one kernel launch (sweeps
+ * over cluster sizes and what-if states).  Instance i owns the jobs
+ * [offsets[i], offsets[i+1]) of the per-job arrays (CSR: count + 1 entries,
+ * offsets[0] = 0, never decreasing; an empty instance is allowed and yields
+ * the level (0, 0)) and num_workers[i] workers.  levels (optional) is
+ * [count][2].  Every instance's result is bit for bit that of the single
+ * call.  Synchronous; count = 0 is a no-op.
+ */
+int sw_ftf_allocate_batch(sw_handle* h, int32_t count, const int64_t* offsets,
+                          const int32_t* num_workers, const int32_t* scale_factors,
+                          const double* full_time, const double* elapsed,
+                          const double* isolated_time, double* allocation, double* levels);
+
 #ifdef __cplusplus
 }
 #endif

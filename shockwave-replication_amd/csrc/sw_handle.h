@@ -127,10 +127,14 @@ struct sw_handle {
     sw_shard_state* shard = nullptr;
     /* MaxMinFairness allocation buffers (sw_mmf.hip) */
     void* mmf = nullptr;
+    /* FinishTimeFairness allocation buffers (sw_ftf.hip) */
+    void* ftf = nullptr;
 };
 
 /* sw_shard.hip: frees the sharded-mode state and communicator */
 void sw_shard_release(sw_handle* h);
 /* sw_mmf.hip: frees the MaxMinFairness buffers */
 void sw_mmf_release(sw_handle* h);
+/* sw_ftf.hip: frees the FinishTimeFairness buffers */
+void sw_ftf_release(sw_handle* h);
 

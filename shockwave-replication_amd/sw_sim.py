@@ -4,7 +4,8 @@ Restates the part of the reference's ``Scheduler.simulate()``
 (scheduler/scheduler.py:1365-1796) that the Shockwave comparison runs:
 trace-driven arrivals, fixed-length rounds on a homogeneous v100 cluster,
 the Shockwave policy (plan solve on the GPU through ShockwaveScheduler) and
-the Gavel MaxMinFairness baseline (allocation LP + deficit-based priorities),
+the Gavel MaxMinFairness and FinishTimeFairness (Themis) baselines (allocation
+program + deficit-based priorities),
 dynamic batch-size scaling (GNS / Accordion) and the Fig-9 metrics.
 
 What is kept from the reference, and where it lives:
@@ -28,7 +29,10 @@ ints; the reference's ``JobIdPair(i, None)`` hashes and compares equal to
 The policy decisions go through pluggable objects so the same loop runs with
 the product solvers (HIP, default) or with the CPU oracles (tests only):
   * Shockwave: ``ShockwaveScheduler(config, solver=…)``;
-  * MaxMinFairness: ``mmf_allocator(scale_factors, coefficients, G) → x``.
+  * MaxMinFairness: ``mmf_allocator(scale_factors, coefficients, G) → x``;
+  * FinishTimeFairness: ``ftf_allocator.ftf_allocate(scale_factors, full_time,
+    elapsed, isolated_time, G) → (x, ρ*, μ)`` (the engine of the policy mirror
+    finish_time_fairness.py).
 """
 from __future__ import annotations
 
@@ -50,24 +54,27 @@ BS_SMALL = 1
 MAX_FAILED_ATTEMPTS = 5  # scheduler.py:49
 WORKER_TYPE = "v100"  # the Shockwave hooks hard-code it (scheduler.py:1000, :3609)
 
-POLICY_NAMES = {"shockwave": "Shockwave", "max_min_fairness": "MaxMinFairness"}
+POLICY_NAMES = {"shockwave": "Shockwave", "max_min_fairness": "MaxMinFairness",
+                "finish_time_fairness": "FinishTimeFairness"}
 
 
 class Simulator:
     """One simulated cluster run (the reference's ``Scheduler`` with
     ``simulate=True``).
 
-    policy:           "shockwave" or "max_min_fairness" (utils.get_policy names)
+    policy:           "shockwave", "max_min_fairness" or "finish_time_fairness"
+                      (utils.get_policy names)
     throughputs:      {(job_type, scale_factor): v100 steps/s} (sw_trace.load_throughputs)
     profiles:         {int job id: profile dict} (the trace pickle; sw_trace.synthesize_profiles)
     shockwave_config: the JSON config + time_per_iteration + num_gpus (driver :60-70)
     shockwave_solver: solver object for ShockwaveScheduler (default: the HIP solver)
     mmf_allocator:    MaxMinFairness allocation function (default: the HIP kernel)
+    ftf_allocator:    FinishTimeFairness engine with ftf_allocate (default: the HIP solver)
     """
 
     def __init__(self, policy, throughputs, profiles, time_per_iteration=120,
                  shockwave_config=None, shockwave_solver=None, mmf_allocator=None,
-                 minimum_time_between_allocation_resets=1920, verbose=False):
+                 minimum_time_between_allocation_resets=1920, verbose=False, ftf_allocator=None):
         if policy not in POLICY_NAMES:
             raise ValueError(f"Unknown policy {policy!r} (supported: {sorted(POLICY_NAMES)})")
         self.policy_name = POLICY_NAMES[policy]
@@ -114,6 +121,8 @@ class Simulator:
         else:
             self._shockwave = None
         self._mmf_allocator = mmf_allocator
+        self._ftf_allocator = ftf_allocator
+        self._ftf_policy = None
 
     # ---- helpers ------------------------------------------------------------------
     def _log(self, msg):
@@ -328,6 +337,8 @@ class Simulator:
         proportional throughput of each job is then 1.0 (proportional.py:27-44),
         so the LP is  max min_j c_j x_j  s.t.  Σ_j sf_j x_j ≤ G, 0 ≤ x_j ≤ 1
         with c_j = sf_j / priority_weight_j.  Jobs in sorted id order."""
+        if self.policy_name == "FinishTimeFairness":
+            return self._compute_ftf_allocation()
         ids = sorted(self._jobs.keys())
         if not ids:
             return {}
@@ -345,6 +356,37 @@ class Simulator:
         self.num_solves += 1
         self.solve_seconds += time.perf_counter() - t0
         return {j: min(1.0, max(0.0, float(v))) for j, v in zip(ids, x)}
+
+    def _compute_ftf_allocation(self):
+        """scheduler.py:2351-2428 → policies/finish_time_fairness.py:14-140: the
+        allocation state (_get_allocation_state) handed to the policy mirror,
+        which keeps the reference's per-job state between calls."""
+        if self._ftf_policy is None:
+            try:
+                from . import sw_native
+                from .finish_time_fairness import FinishTimeFairnessPolicy
+            except ImportError:
+                import sw_native
+                from finish_time_fairness import FinishTimeFairnessPolicy
+            if self._ftf_allocator is None:
+                self._ftf_allocator = sw_native.Solver(device=0)
+            self._ftf_policy = FinishTimeFairnessPolicy(native=self._ftf_allocator)
+        jobs = self._jobs
+        throughputs = {j: {WORKER_TYPE: self._throughputs[j]} for j in jobs}
+        scale_factors = {j: jobs[j].scale_factor for j in jobs}
+        priority_weights = {j: jobs[j].priority_weight for j in jobs}
+        num_steps_remaining = {j: self._remaining_steps(j) for j in jobs}
+        times_since_start = {j: self._current_timestamp - self._per_job_start_timestamps[j] for j in jobs}
+        cluster_spec = {WORKER_TYPE: len(self._worker_ids)}
+        import time
+        t0 = time.perf_counter()
+        allocation = self._ftf_policy.get_allocation(throughputs, scale_factors, priority_weights,
+                                                     times_since_start, num_steps_remaining, cluster_spec)
+        if allocation is None:
+            return {}
+        self.num_solves += 1
+        self.solve_seconds += time.perf_counter() - t0
+        return {j: float(allocation[j][WORKER_TYPE]) for j in allocation}
 
     def _reset_time_run_so_far(self):
         """scheduler.py:2589-2638."""
@@ -572,7 +614,7 @@ class Simulator:
 
 def run_trace(policy, trace_file, num_gpus, time_per_iteration=120, config=None,
               throughputs=None, shockwave_solver=None, mmf_allocator=None, max_jobs=None,
-              verbose=False):
+              verbose=False, ftf_allocator=None):
     """The driver's main() (simulate_scheduler_with_trace.py:27-133): parse the
     trace, synthesise the profiles (the missing pickle), set job durations from
     them (:37-39), simulate, and return the Fig-9 metrics."""
@@ -590,6 +632,6 @@ def run_trace(policy, trace_file, num_gpus, time_per_iteration=120, config=None,
         sw_config["num_gpus"] = num_gpus
     sim = Simulator(policy, tp, profiles, time_per_iteration=time_per_iteration,
                     shockwave_config=sw_config, shockwave_solver=shockwave_solver,
-                    mmf_allocator=mmf_allocator, verbose=verbose)
+                    mmf_allocator=mmf_allocator, verbose=verbose, ftf_allocator=ftf_allocator)
     sim.simulate(num_gpus, arrivals, jobs)
     return sim.summary()

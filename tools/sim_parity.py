@@ -45,7 +45,8 @@ def main():
     ap.add_argument("--trace", default="220_0.2_5_100_25_4_0,0.5,0.5_0.6,0.3,0.09,0.01_multigpu_dynamic.trace")
     ap.add_argument("--gpus", type=int, default=64)
     ap.add_argument("--solver", choices=["gpu", "twin", "milp"], default="gpu")
-    ap.add_argument("--policies", default="shockwave,max_min_fairness")
+    ap.add_argument("--policies", default="shockwave,max_min_fairness",
+                    help="comma-separated: shockwave, max_min_fairness, finish_time_fairness")
     ap.add_argument("--max-jobs", type=int, default=None)
     ap.add_argument("--time-per-iteration", type=int, default=120)
     ap.add_argument("--future-rounds", type=int, default=None,
@@ -61,9 +62,13 @@ def main():
         import sw_native as sn
         solver = sn.Solver(device=0)
         mmf = sn.MmfAllocator(solver=solver)
+        ftf = solver
     else:
         import mmf_ref
         mmf = mmf_ref.twin_allocator
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import ftf_ref
+        ftf = ftf_ref.TwinEngine()
         if a.solver == "twin":
             solver = twin_solver()
         else:
@@ -77,7 +82,7 @@ def main():
         with contextlib.redirect_stdout(io.StringIO()):
             r = sw_sim.run_trace(pol, trace, a.gpus, a.time_per_iteration, cfg,
                                  shockwave_solver=solver, mmf_allocator=mmf,
-                                 max_jobs=a.max_jobs)
+                                 max_jobs=a.max_jobs, ftf_allocator=ftf)
         r["wall_s"] = time.time() - t0
         out["runs"][pol] = r
         print(pol, json.dumps(r), flush=True)
