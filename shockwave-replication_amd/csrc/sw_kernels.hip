@@ -31,6 +31,7 @@
 
 #include "../../include/shockwave_amd.h"
 #include "sw_arith.h"
+#include "sw_rowsearch.h"
 #include "sw_block.h"
 #include "sw_device.h"
 #include "sw_pack.h"
@@ -231,10 +232,7 @@ struct Ctx {
     __device__ __forceinline__ uint32_t kbits(int j, int s, int n) const {
         if constexpr (ONE) {
             (void)j;
-            uint32_t v = 0;
-#pragma unroll
-            for (int i = 0; i < KT; ++i) v = (i == n) ? sw_fbits_of(kr[s][i]) : v;
-            return v;
+            return sw_rs_extract<KT>(kr[s], n);
         } else {
             (void)s;
             return sw_fbits_of(gkeys[(size_t)j * KT + n]);
@@ -316,17 +314,14 @@ struct Ctx {
     /* twin: cnt_gt / cnt_ge.  Keys are nonincreasing, so the items with
      * key > ρ (≥ ρ) form a prefix [0, c) and the count over [l, Tj) is
      * min(c, Tj) − l, clamped at 0.  On chip the register row is zero past
-     * Tj, so c needs one compare per key. */
+     * Tj, so c is a binary search over the whole row, written as a select
+     * tree (sw_rowsearch.h). */
     template <bool GE>
     __device__ __forceinline__ int cnt(int j, int s, uint32_t rho, int l) const {
         const int tj = Tj(j, s);
         int c = 0;
         if constexpr (ONE) {
-#pragma unroll
-            for (int n = 0; n < KT; ++n) {
-                const uint32_t b = sw_fbits_of(kr[s][n]);
-                c += (GE ? (b >= rho) : (b > rho)) ? 1 : 0;
-            }
+            c = sw_rs_count<GE, KT>(kr[s], rho);
             c = (c < tj ? c : tj) - l;
             c = c > 0 ? c : 0;
         } else {
@@ -353,18 +348,10 @@ struct Ctx {
         if constexpr (ONE) {
             (void)j;
             /* the keys > mid are the prefix [0, c0): the last of them is
-             * row[c0 − 1] and the key after it row[c0] (0 past the row), so
-             * two selects on the compare, no min / max per key */
-            uint32_t lo_k = 0x7FFFFFFFu, hi_k = sw_fbits_of(kr[s][0]);
-#pragma unroll
-            for (int n = 0; n < KT; ++n) {
-                const uint32_t b = sw_fbits_of(kr[s][n]);
-                const uint32_t nx = n + 1 < KT ? sw_fbits_of(kr[s][n + 1 < KT ? n + 1 : n]) : 0u;
-                const bool gt = b > mid;
-                c += gt ? 1 : 0;
-                lo_k = gt ? b : lo_k;
-                hi_k = gt ? nx : hi_k;
-            }
+             * row[c0 − 1] and the key after it row[c0] (0 past the row), the
+             * last pivots of the search either side of the split */
+            uint32_t lo_k, hi_k;
+            c = sw_rs_count_snap<KT>(kr[s], mid, lo_k, hi_k);
             mn = min(mn, (int32_t)lo_k);
             mx = max(mx, (int32_t)hi_k);
         } else {
@@ -503,7 +490,7 @@ struct Ctx {
                 /* Per-job windows: ca = #keys ≥ lo (= count above lo − 1),
                  * cb = #keys > hi.  Every probe mid ∈ [lo, hi) counts
                  * between them, so a job whose window is closed (ca == cb)
-                 * skips its 32 compares; as the bracket narrows, whole
+                 * skips its row search; as the bracket narrows, whole
                  * waves skip.  Same probes, same ρ*. */
                 int ca[SW_JPT], cb[SW_JPT], cm[SW_JPT];
 #pragma unroll
