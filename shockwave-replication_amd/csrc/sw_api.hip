@@ -28,13 +28,17 @@
 #include "sw_p2x.h"
 #include "sw_validate.h"
 
+/* An integer knob from the environment (def when unset); every caller reads
+ * its knob once, into a static. */
+static int env_int(const char* name, int def) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : def;
+}
+
 /* on-chip batches up to this many instances (one per CU) fuse the exchange
  * step into the full kernel (SW_FUSE_MAX overrides) */
 static int fuse_max_count() {
-    static const int v = [] {
-        const char* e = getenv("SW_FUSE_MAX");
-        return e ? atoi(e) : 256;
-    }();
+    static const int v = env_int("SW_FUSE_MAX", 256);
     return v;
 }
 
@@ -46,10 +50,7 @@ static int fuse_max_count() {
  * instance C5 sweep with its slow small-cluster instances) one full kernel
  * is faster. */
 static int split_min_count() {
-    static const int v = [] {
-        const char* e = getenv("SW_SPLIT_MIN");
-        return e ? atoi(e) : 256;
-    }();
+    static const int v = env_int("SW_SPLIT_MIN", 256);
     return v;
 }
 
@@ -64,19 +65,15 @@ static int split_min_count() {
  * −1.5 %, 4,096 +5.2 %, 8,192 (a host-boundary chunk) +7.5 %, 32,768 +8.7 %
  * — so from 4,096. */
 static int loop_min_count() {
-    static const int v = [] {
-        const char* e = getenv("SW_LOOP_MIN");
-        return e ? atoi(e) : 4096;
-    }();
+    static const int v = env_int("SW_LOOP_MIN", 4096);
     return v;
 }
 
-extern "C" size_t sw_plan_kernel_lds_bytes(int one);
-extern "C" hipError_t sw_launch_plan(const sw_batch_dev* B, int KT, int one, size_t lds,
-                                     hipStream_t stream);
-extern "C" hipError_t sw_launch_split(sw_batch_dev* B, size_t p2x_lds, hipStream_t stream);
+/* the launches (sw_kernels.hip, sw_p2x_kernel.hip) size their own LDS from
+ * the batch's largest instance */
+extern "C" hipError_t sw_launch_plan(const sw_batch_dev* B, int maxN, int maxT, hipStream_t stream);
+extern "C" hipError_t sw_launch_split(sw_batch_dev* B, int maxN, int maxT, hipStream_t stream);
 extern "C" hipError_t sw_launch_p2x(const sw_batch_dev* B, int maxN, int maxT, hipStream_t stream);
-extern "C" size_t sw_p2x_kernel_lds_bytes(int maxN, int maxT);
 
 namespace {
 
@@ -265,8 +262,7 @@ namespace {
  * most 16 (a GPU's CPU share on the MI355X box; SW_HOST_THREADS overrides). */
 int host_threads(int64_t jobs) {
     static const int cap = [] {
-        const char* e = getenv("SW_HOST_THREADS");
-        const int v = e ? atoi(e) : 0;
+        const int v = env_int("SW_HOST_THREADS", 0);
         if (v > 0) return std::min(v, 256);
         const unsigned hw = std::thread::hardware_concurrency();
         return (int)std::max(1u, std::min(hw ? hw : 1u, 16u));
@@ -346,7 +342,7 @@ int prepare_batch(sw_handle* h, int32_t count, const sw_problem* probs) {
         h->d_masks.reserve(Jz) || h->d_nb.reserve(Jz) || h->d_lvl.reserve(std::max(count, 1)) ||
         h->d_lws.reserve(Jz) || h->d_lwm.reserve(Jz) || h->d_lwa.reserve(std::max(count, 1)))
         return fail(h, SW_ERR_HIP, "device allocation failed");
-    if (maxN > SW_LDS_JOBS || maxT > 32) {
+    if (!sw_on_chip(maxN, maxT)) {
         const int KT = maxT <= 32 ? 32 : 64;
         if (h->d_ws_u8.reserve(Jz * SW_WS_U8) || h->d_ws_u64.reserve(Jz * SW_WS_U64 + (size_t)SW_WS_PAD_U64 * std::max(count, 1)) ||
             h->d_ws_sort.reserve(Jz * 4) || h->d_ws_keys.reserve(Jz * KT) ||
@@ -499,7 +495,7 @@ int launch(sw_handle* h, int32_t lo, int32_t hi, hipStream_t s, bool timed, bool
 #ifdef SW_STAMPS
     B.stamps = h->d_stamps.p + (size_t)lo * SW_STAMP_SLOTS;
 #endif
-    const int one = h->maxN <= SW_LDS_JOBS && h->maxT <= 32;
+    const bool one = sw_on_chip(h->maxN, h->maxT);
     if (!one) {
         B.ws.u8 = h->d_ws_u8.p;
         B.ws.u64 = h->d_ws_u64.p;
@@ -508,7 +504,6 @@ int launch(sw_handle* h, int32_t lo, int32_t hi, hipStream_t s, bool timed, bool
         B.ws.jc = h->d_ws_jc.p;
     }
     B.p2ws = h->d_p2ws.p;
-    size_t lds = sw_plan_kernel_lds_bytes(one);
     if (timed) {
         if (h->ev_used == kEventPairs && collect_timing(h) != SW_OK) return SW_ERR_HIP;
         SW_HIP(h, hipEventRecord(h->ev_pool[2 * h->ev_used], s));
@@ -535,9 +530,7 @@ int launch(sw_handle* h, int32_t lo, int32_t hi, hipStream_t s, bool timed, bool
 #endif
     B.fuse_p2x = one && (split || B.count <= fuse_max_count()); /* split: always fused */
     B.loop_split = split && B.count >= loop_min_count();
-    if (B.fuse_p2x) lds = std::max(lds, sw_p2x_kernel_lds_bytes(h->maxN, h->maxT));
-    hipError_t e = split ? sw_launch_split(&B, sw_p2x_kernel_lds_bytes(h->maxN, h->maxT), s)
-                         : sw_launch_plan(&B, B.KT, one, lds, s);
+    hipError_t e = split ? sw_launch_split(&B, h->maxN, h->maxT, s) : sw_launch_plan(&B, h->maxN, h->maxT, s);
     if (e != hipSuccess) return hip_fail(h, e, "plan kernel launch");
     if (timed) {
         SW_HIP(h, hipEventRecord(h->ev_pool[2 * h->ev_used + 1], s));
@@ -629,8 +622,7 @@ void mark_loaded(sw_handle* h) {
 /* Chunks of a host-boundary solve (SW_PIPELINE_CHUNKS overrides; 1 = none). */
 int pipeline_chunks(int32_t count) {
     static const int req = [] {
-        const char* e = getenv("SW_PIPELINE_CHUNKS");
-        const int v = e ? atoi(e) : 0;
+        const int v = env_int("SW_PIPELINE_CHUNKS", 0);
         return v > 0 ? std::min(v, kMaxChunks) : 4;
     }();
     /* chunks of at least 2048 instances: each launch keeps every CU busy */
@@ -696,15 +688,11 @@ int solve_pipelined(sw_handle* h, int32_t count, const sw_problem* probs, sw_res
 constexpr int kMaxRunStreams = 4; /* GPU_MAX_HW_QUEUES is 4 on the box */
 
 int run_streams(const sw_handle* h) {
-    static const int req = [] {
-        const char* e = getenv("SW_RUN_STREAMS");
-        return e ? atoi(e) : -1;
-    }();
+    static const int req = env_int("SW_RUN_STREAMS", -1);
 #ifdef SW_STAMPS
     return 1; /* diagnostic builds time the phases inside the full kernel */
 #endif
-    const bool one = h->maxN <= SW_LDS_JOBS && h->maxT <= 32;
-    if (!one || h->count <= split_min_count()) return 1; /* not a split batch */
+    if (!sw_on_chip(h->maxN, h->maxT) || h->count <= split_min_count()) return 1; /* not a split batch */
     int ns = req >= 0 ? req : (h->count <= 2048 ? 2 : 1);
     ns = std::max(1, std::min(ns, kMaxRunStreams));
     return std::min(ns, std::max(1, h->count / 64)); /* chunks of at least 64 */
@@ -825,7 +813,7 @@ int sw_plan_solve_batch(sw_handle* h, int32_t count, const sw_problem* probs, sw
             maxN = std::max(maxN, probs[i].num_jobs);
             maxT = std::max(maxT, probs[i].future_rounds);
         }
-        if (maxN <= SW_LDS_JOBS && maxT <= 32) {
+        if (sw_on_chip(maxN, maxT)) {
             int rc = validate_all(h, probs, count);
             if (rc != SW_OK) return rc;
             if ((rc = prepare_batch(h, count, probs)) != SW_OK) return rc;

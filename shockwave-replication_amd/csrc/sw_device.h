@@ -21,6 +21,9 @@
 
 #define SW_STAMP_SLOTS 64 /* per-instance u64 slots of the SW_STAMPS diagnostic build (32…42: sw_p2x_kernel, 48…52: pack sub-phases) */
 #define SW_LDS_JOBS 1024 /* instances up to this many jobs keep all state on chip (2 per thread) */
+/* A batch whose largest instance has maxN jobs and maxT rounds runs on chip:
+ * per-job state in LDS, 32-key rows in registers; otherwise the workspace path. */
+inline bool sw_on_chip(int maxN, int maxT) { return maxN <= SW_LDS_JOBS && maxT <= 32; }
 
 struct sw_inst_dev {
     int32_t N, T, G, nb;
@@ -35,6 +38,21 @@ struct sw_out_dev {
     double objective, utility, makespan, p2_objective, bound;
     int32_t iters, status;
 };
+
+/* Σ_t t·bit_t of a round mask: bit b of t weighted 2^b, six popcounts.  At
+ * most 2016, summed in 32 bits: as a 64-bit value returned from a helper the
+ * sum took 64-bit adds and the two-part conversion to double, and
+ * sw_pack_kernel ran 0.9 % slower on the C5 sweep. */
+__device__ __forceinline__ int32_t sw_mask_tsum(uint64_t m) {
+    return __popcll(m & 0xAAAAAAAAAAAAAAAAull) + 2 * __popcll(m & 0xCCCCCCCCCCCCCCCCull) +
+           4 * __popcll(m & 0xF0F0F0F0F0F0F0F0ull) + 8 * __popcll(m & 0xFF00FF00FF00FF00ull) +
+           16 * __popcll(m & 0xFFFF0000FFFF0000ull) + 32 * __popcll(m & 0xFFFFFFFF00000000ull);
+}
+/* A job's term of the P2 objective: the mean round of its mask m (cnt > 0
+ * rounds) weighted by its priority p. */
+__device__ __forceinline__ double sw_p2_term(uint64_t m, int cnt, double p) {
+    return ((double)sw_mask_tsum(m) / (double)cnt) * p;
+}
 
 /* Global workspace, per job (used only when N > SW_LDS_JOBS). */
 struct sw_ws_dev {

@@ -106,20 +106,18 @@ __device__ __forceinline__ uint32_t st_sel(uint32_t s) { return (s >> 16) & 1u; 
  * thread's two jobs sit side by side, so one field of both is one 16-byte LDS
  * read, and the 34 VGPRs a register copy would pin stay free for the
  * searches and the packer. */
+struct sw_job_soa { /* the LDS region (the JL field of the layouts below) */
+    double rate[SW_LDS_JOBS], cap[SW_LDS_JOBS], d[SW_LDS_JOBS], R[SW_LDS_JOBS], a[SW_LDS_JOBS],
+        Fd[SW_LDS_JOBS], Ed[SW_LDS_JOBS], invE[SW_LDS_JOBS];
+    int32_t w[SW_LDS_JOBS];
+};
 struct sw_job_lds {
     double *rate, *cap, *d, *R, *a, *Fd, *Ed, *invE;
     int32_t* w;
-    template <class Carve>
-    __device__ __forceinline__ void carve(Carve&& cv) {
-        rate = (double*)cv(8 * SW_LDS_JOBS);
-        cap = (double*)cv(8 * SW_LDS_JOBS);
-        d = (double*)cv(8 * SW_LDS_JOBS);
-        R = (double*)cv(8 * SW_LDS_JOBS);
-        a = (double*)cv(8 * SW_LDS_JOBS);
-        Fd = (double*)cv(8 * SW_LDS_JOBS);
-        Ed = (double*)cv(8 * SW_LDS_JOBS);
-        invE = (double*)cv(8 * SW_LDS_JOBS);
-        w = (int32_t*)cv(4 * SW_LDS_JOBS);
+    __device__ __forceinline__ void at(unsigned char* p) {
+        sw_job_soa* S = reinterpret_cast<sw_job_soa*>(p);
+        rate = S->rate; cap = S->cap; d = S->d; R = S->R; a = S->a;
+        Fd = S->Fd; Ed = S->Ed; invE = S->invE; w = S->w;
     }
     __device__ __forceinline__ sw_jobc get(int j) const {
         sw_jobc c;
@@ -132,7 +130,6 @@ struct sw_job_lds {
         Fd[j] = c.Fd; Ed[j] = c.Ed; invE[j] = c.invE; w[j] = c.w;
     }
 };
-#define SW_JOB_LDS_BYTES (8 * 8 * SW_LDS_JOBS + 4 * SW_LDS_JOBS)
 
 /* jobs per thread on the on-chip path (N ≤ SW_LDS_JOBS = SW_JPT · SW_BLOCK) */
 #define SW_JPT 2
@@ -190,6 +187,98 @@ struct Ctx {
     /* per-job data in HBM (!ONE) */
     float* gkeys;
     sw_jobc* gjc;
+
+    /* The instance's scalars and inputs; every LDS / workspace pointer starts
+     * null and each kernel sets the regions it has. */
+    __device__ __forceinline__ void init(const sw_batch_dev& B, const sw_inst_dev* I) {
+        inst = I;
+        N = I->N;
+        T = I->T;
+        G = I->G;
+        nb = I->nb;
+        C = (int64_t)I->G * I->T;
+        k = I->k;
+        inv_delta = 1.0 / I->delta;
+        passes = 0;
+        q = (N + SW_BLOCK - 1) / SW_BLOCK;
+        w_in = B.w + I->job_off;
+        p_in = B.p + I->job_off;
+#ifdef SW_STAMPS
+        swp = nullptr;
+        lsp = nullptr;
+#endif
+        blk.X = nullptr;
+        blk.par = 0;
+        beta = ell = slope = nullptr;
+        ncur = lcur = tkcur = nbest = placed = placed2 = nfin = tiecur = nullptr;
+        ycur = ybest = y2 = nullptr;
+        pst = nullptr;
+        pmask = nullptr;
+        pord = nullptr;
+        sbuf = nullptr;
+        H = SH = caps = nullptr;
+        PL = nullptr;
+        pwc = 0;
+        misc = nullptr;
+        rep = nullptr;
+        bnb = nullptr;
+        JL = sw_job_lds{};
+        gkeys = nullptr;
+        gjc = nullptr;
+    }
+    /* the pack state at p: histograms, and its spare row for the class capacities */
+    __device__ __forceinline__ void set_pack_lds(unsigned char* p) {
+        PL = (sw_pack_lds*)p;
+        H = PL->H[0];
+        SH = PL->SH[0];
+        caps = PL->H[1];
+    }
+    /* β, ℓ and the segment slopes (sw_pwl_slopes, one segment per thread:
+     * the same IEEE division) into the table bt; read after the next barrier */
+    __device__ __forceinline__ void fill_pwl(double* bt) {
+        beta = bt;
+        ell = bt + SW_BMAX;
+        slope = bt + 2 * SW_BMAX;
+        if (threadIdx.x < SW_BMAX) {
+            const int b = (int)threadIdx.x;
+            bt[b] = inst->beta[b];
+            bt[SW_BMAX + b] = inst->ell[b];
+            bt[2 * SW_BMAX + b] =
+                b < inst->nb - 1 ? (inst->ell[b + 1] - inst->ell[b]) / (inst->beta[b + 1] - inst->beta[b]) : 0.0;
+        }
+    }
+    /* the on-chip per-job constants at p: every slot < SW_LDS_JOBS holds a
+     * valid record (a dummy past N) */
+    __device__ __forceinline__ void fill_job_lds(const sw_batch_dev& B, unsigned char* p) {
+        JL.at(p);
+        const int64_t jo = inst->job_off;
+        for (int j = threadIdx.x; j < SW_LDS_JOBS; j += SW_BLOCK)
+            JL.put(j, j < N ? sw_make_jobc(N, T, inst->delta, B.w[jo + j], B.d[jo + j], B.F[jo + j],
+                                           B.E[jo + j], B.R[jo + j], B.p[jo + j])
+                            : sw_make_jobc(1, 1, 1.0, 1, 1.0, 0, 1, 0.0, 0.0));
+    }
+    /* twin: plan_objective — U = Σ_j f_j(n_j), M = max_j g_j(n_j) of the
+     * counts n in one reduction; returns J = U − k·M.  One pass (PASS: counted
+     * where the twin counts it). */
+    template <bool PASS = true>
+    __device__ __forceinline__ double plan_objective(const uint8_t* n, double& U, double& M) {
+        return plan_objective<PASS>(n, U, M, [](int, int) {});
+    }
+    /* ... with the caller's per-job work also(j, s) in the same loop, ahead of
+     * the read of n[j]: a second walk over workspace rows costs the workspace
+     * kernels registers (181 against 178 VGPRs) */
+    template <bool PASS = true, class F>
+    __device__ __forceinline__ double plan_objective(const uint8_t* n, double& U, double& M, F&& also) {
+        double fs = 0.0, gm = 0.0;
+        for_jobs([&](int j, int s) {
+            also(j, s);
+            fs = fs + fval(j, s, n[j]);
+            gm = sw_max(gm, gval(j, s, n[j]));
+        });
+        blk.detsum_max(fs, gm, U, M);
+        if (PASS) passes++;
+        return U - k * M;
+    }
 
     __device__ __forceinline__ int jlo() const { return (int)threadIdx.x * q; }
     __device__ __forceinline__ int jhi() const {
@@ -1563,34 +1652,275 @@ struct Ctx {
             wave_sync();
         }
     }
+
+    /* ---- the steps of twin_plan_solve after the P1 loop: the best P1 plan
+     *      is nfin / ybest; nbest, ycur, placed, placed2, y2 are scratch ---- */
+
+    /* twin: fill_stranded — a re-solved P1 can leave round capacity idle; add
+     * single rounds there, largest utility gain first (sw_fill_key), one
+     * block max per round.  Returns the rounds added. */
+    __device__ __forceinline__ int fill_stranded() {
+        int32_t* load = caps; /* spare pack row, free until class-wise P2 */
+        if (threadIdx.x < 64) load[threadIdx.x] = 0;
+        __syncthreads();
+        for_jobs([&](int j, int s) {
+            const uint64_t m = ybest[j];
+            const int32_t w = jc(j, s).w;
+            for (int t = 0; t < T; ++t)
+                if ((m >> t) & 1ull) atomicAdd(&load[t], w);
+        });
+        __syncthreads();
+        int added = 0;
+        for (int step = 0; step < SW_FILL_MAX; ++step) {
+            uint64_t best = 0;
+            for_jobs([&](int j, int s) {
+                const int n = nfin[j];
+                if (n >= Tj(j, s)) return;
+                const uint64_t m = ybest[j];
+                const int32_t w = jc(j, s).w;
+                int tf = -1;
+                for (int t = 0; t < T; ++t)
+                    if (!((m >> t) & 1ull) && w <= G - load[t]) { tf = t; break; }
+                if (tf < 0) return;
+                const uint64_t key = sw_fill_key(fval(j, s, n + 1) - fval(j, s, n), j, tf);
+                best = key > best ? key : best;
+            });
+            best = blk.umax(best); /* its barrier: every thread has read load */
+            passes++;
+            if (best == 0) break;
+            const int jb = (int)sw_fill_job(best);
+            const int tb = sw_fill_round(best);
+            if (jb >= jlo() && jb < jhi()) {
+                ybest[jb] |= 1ull << tb;
+                nfin[jb] = (uint8_t)(nfin[jb] + 1);
+            }
+            if (threadIdx.x == 0) load[tb] += w_in[jb];
+            ++added;
+            __syncthreads();
+        }
+        return added;
+    }
+
+    /* twin: raise_counts (sw_arith.h SW_RAISE_ITERS) — one job one more
+     * round, the whole plan re-placed by the pattern search (scratch pscr).
+     * The try's counts go to nbest, its placement to ycur / placed; every
+     * decision is a block reduction.  Returns the raises kept. */
+    __device__ __forceinline__ int raise_counts(int32_t* pscr) {
+        int kept = 0;
+        for (int rit = 0; rit < SW_RAISE_ITERS; ++rit) {
+            double U, M;
+            int64_t ld_l = 0;
+            const double J =
+                plan_objective(nfin, U, M, [&](int j, int s) { ld_l += (int64_t)jc(j, s).w * nfin[j]; });
+            const int64_t load = blk.sum(ld_l);
+            int32_t i1l = 0x7FFFFFFF; /* the first job attaining M, and the others' max */
+            for_jobs([&](int j, int s) {
+                if (j < i1l && gval(j, s, nfin[j]) == M) i1l = j;
+            });
+            const int32_t i1 = blk.min32(i1l);
+            double m2l = 0.0;
+            for_jobs([&](int j, int s) {
+                if (j != i1) m2l = sw_max(m2l, gval(j, s, nfin[j]));
+            });
+            const double M2 = blk.dmax(m2l);
+            int32_t tried[SW_RAISE_TRIES];
+            bool took = false;
+            for (int tr = 0; tr < SW_RAISE_TRIES && !took; ++tr) {
+                uint64_t kl = 0;
+                for_jobs([&](int j, int s) {
+                    const int n = nfin[j];
+                    if (n >= Tj(j, s)) return;
+                    for (int i = 0; i < tr; ++i)
+                        if (tried[i] == j) return;
+                    const double Mo = j == i1 ? M2 : M;
+                    const uint64_t key = sw_fill_key(
+                        sw_raise_gain(fval(j, s, n), fval(j, s, n + 1), gval(j, s, n + 1), Mo, M, k), j, 0);
+                    kl = key > kl ? key : kl;
+                });
+                const uint64_t best = blk.umax(kl);
+                if (best == 0) break; /* uniform */
+                const int b = (int)sw_fill_job(best);
+                tried[tr] = b;
+                if (load + w_in[b] > (int64_t)G * T) continue;
+                /* pattern_pack rewrites the rows of the jobs with rounds; the
+                 * others' rows (scratch of the re-optimisation) are cleared, as
+                 * the twin's pattern_pack clears its output */
+                for_jobs([&](int j, int s) {
+                    (void)s;
+                    nbest[j] = (uint8_t)(nfin[j] + (j == b ? 1 : 0));
+                    ycur[j] = 0;
+                    placed[j] = 0;
+                });
+                if (!pattern_pack(nbest, ycur, placed, pscr)) continue; /* uniform */
+                double U2, M2t;
+                if (plan_objective<false>(placed, U2, M2t) > J) {
+                    for_jobs([&](int j, int s) {
+                        (void)s;
+                        nfin[j] = placed[j];
+                        ybest[j] = ycur[j];
+                    });
+                    took = true;
+                }
+            }
+            __syncthreads();
+            if (!took) break;
+            ++kept;
+        }
+        return kept;
+    }
+
+    /* twin: the P2 block — (a) density order, (b) weight order, (c) class-wise
+     * inside the P1 profile: the first that places every round of nfin, into
+     * y2.  False when none does (the emit then keeps the P1 placement). */
+    __device__ __forceinline__ bool place_p2(bool dens_best, bool rep_best, bool dskip_best,
+                                             int32_t& status) {
+        auto p2_ok = [&]() {
+            int64_t bad_l = 0;
+            for_jobs([&](int j, int s) { (void)s; bad_l += (placed[j] != nfin[j]); });
+            return blk.sum(bad_l) == 0;
+        };
+        bool ok2 = false;
+        if (dens_best) { /* (a) is the P1 placement itself */
+            for_jobs([&](int j, int s) { (void)s; y2[j] = ybest[j]; });
+            ok2 = true;
+            if (rep_best) status |= SW_STATUS_P2_REPAIRED;
+        }
+        for (int att = 0; att < 2 && !ok2; ++att) {
+            if (att == 0 && dskip_best) continue;
+            pack(att == 0 ? 4 : 2, nfin, y2, placed);
+            ok2 = p2_ok();
+            if (!ok2 && att == 0) { /* (a') density with its width profile repaired */
+                ok2 = repair_pack(nfin, y2, placed, ycur, placed2);
+                if (ok2) {
+                    for_jobs([&](int j, int s) { (void)s; y2[j] = ycur[j]; });
+                    status |= SW_STATUS_P2_REPAIRED;
+                }
+            }
+            if (ok2 && att == 1) status |= SW_STATUS_P2_WEIGHT_ORDER;
+        }
+        if (!ok2) {
+            int32_t wprev = 0;
+            while (true) {
+                int32_t wl = 0x7FFFFFFF;
+                for_jobs([&](int j, int s) {
+                    const int32_t w = jc(j, s).w;
+                    if (nfin[j] > 0 && w > wprev && w < wl) wl = w;
+                });
+                const int32_t wc = blk.min32(wl);
+                if (wc == 0x7FFFFFFF) break;
+                __syncthreads(); /* the previous class's pack has read caps */
+                if (threadIdx.x < 64) caps[threadIdx.x] = 0;
+                __syncthreads();
+                for_jobs([&](int j, int s) {
+                    if (nfin[j] > 0 && jc(j, s).w == wc) {
+                        const uint64_t m = ybest[j];
+                        for (int t = 0; t < T; ++t)
+                            if ((m >> t) & 1ull) atomicAdd(&caps[t], 1);
+                    }
+                });
+                pwc = wc;
+                pack(5, nfin, y2, placed);
+                wprev = wc;
+            }
+            ok2 = p2_ok();
+            if (ok2) status |= SW_STATUS_P2_CLASSWISE;
+        }
+        return ok2;
+    }
 };
 
-/* Dynamic LDS of the plan kernel: the carve-up in solve_instance, region by
- * region (16-byte aligned).  The launch sizes the allocation with it and the
- * kernel compares its own carve offset against it (constant-folded). */
-__host__ __device__ constexpr size_t sw_plan_lds_bytes(bool one) {
-    auto r16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    size_t s = r16(sizeof(sw_xchg)) + r16(sizeof(double) * 3 * SW_BMAX) +
-               r16(sizeof(sw_pack_lds)) + r16(sizeof(int64_t) * 8) + r16(sizeof(sw_repair_t));
-    if (one) {
-        const size_t NJ = SW_LDS_JOBS;
-        s += 8 * r16(NJ) + 3 * r16(8 * NJ) + r16(8 * 4 * SW_JPT * SW_BLOCK) + SW_JOB_LDS_BYTES;
-    } else {
-        /* the re-optimisation's knapsack rows and take bits (sw_reround_dev.h;
-         * on chip they reuse the sort buffer and two mask rows) */
-        s += 2 * r16(8 * (SW_RR_CAPMAX + 1)) + r16(8 * SW_RR_WORDS);
-    }
-    return s;
-}
+/*
+ * The dynamic LDS of every kernel here: one constexpr struct of byte offsets
+ * per layout, a field per region (16-byte aligned) and end.  The kernels take
+ * their pointers from it, the launches its end, and the regions that a later
+ * phase reuses are held to their sizes by the static_asserts below.
+ */
+__host__ __device__ constexpr size_t sw_r16(size_t b) { return (b + 15) & ~(size_t)15; }
 
-/* LDS of the level-search kernel: the setup's key staging window (whose
- * space the per-job level-search bytes reuse afterwards) and the per-job
- * constants. */
-__host__ __device__ constexpr size_t sw_level_lds_bytes() {
-    auto r16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    return r16(sizeof(sw_xchg)) + r16(sizeof(double) * 3 * SW_BMAX) +
-           r16(sizeof(float) * SW_JPT * SW_SETUP_CH * SW_BLOCK) + SW_JOB_LDS_BYTES;
+constexpr size_t SW_STAGE_BYTES = sizeof(float) * SW_JPT * SW_SETUP_CH * SW_BLOCK; /* setup()'s window */
+constexpr size_t SW_BNB_BYTES = sizeof(sw_bnb_ivl) * SW_BNB_CAP; /* the level search's interval list */
+
+/* The full plan kernel (solve_instance).  ONE: every per-job array on chip;
+ * else the common head and the re-optimisation's knapsack rows and take bits
+ * (sw_reround_dev.h; on chip they reuse the sort buffer and two mask rows),
+ * the rest in the HBM workspace. */
+struct sw_plan_carve {
+    size_t X, bt, PL, misc, rep;
+    size_t ncur, lcur, tkcur, nbest, placed, placed2, nfin, tiecur, ycur, ybest, y2, sbuf, JL; /* ONE */
+    size_t rr_dpA, rr_dpB, rr_bits;                                                           /* !ONE */
+    size_t end;
+};
+template <bool ONE>
+__host__ __device__ constexpr sw_plan_carve sw_plan_offsets() {
+    const size_t NJ = SW_LDS_JOBS;
+    sw_plan_carve o{};
+    size_t off = 0;
+    o.X = off;    off += sw_r16(sizeof(sw_xchg));
+    o.bt = off;   off += sw_r16(sizeof(double) * 3 * SW_BMAX);
+    o.PL = off;   off += sw_r16(sizeof(sw_pack_lds));
+    o.misc = off; off += sw_r16(sizeof(int64_t) * 8);
+    o.rep = off;  off += sw_r16(sizeof(sw_repair_t));
+    if (ONE) {
+        o.ncur = off;    off += sw_r16(NJ);
+        o.lcur = off;    off += sw_r16(NJ);
+        o.tkcur = off;   off += sw_r16(NJ);
+        o.nbest = off;   off += sw_r16(NJ);
+        o.placed = off;  off += sw_r16(NJ);
+        o.placed2 = off; off += sw_r16(NJ);
+        o.nfin = off;    off += sw_r16(NJ);
+        o.tiecur = off;  off += sw_r16(NJ);
+        o.ycur = off;    off += sw_r16(8 * NJ);
+        o.ybest = off;   off += sw_r16(8 * NJ);
+        o.y2 = off;      off += sw_r16(8 * NJ);
+        o.sbuf = off;    off += sw_r16(8 * 4 * SW_JPT * SW_BLOCK); /* [2][2][1024] bitonic exchange */
+        o.JL = off;      off += sw_r16(sizeof(sw_job_soa));
+    } else {
+        o.rr_dpA = off;  off += sw_r16(8 * (SW_RR_CAPMAX + 1));
+        o.rr_dpB = off;  off += sw_r16(8 * (SW_RR_CAPMAX + 1));
+        o.rr_bits = off; off += sw_r16(8 * SW_RR_WORDS);
+    }
+    o.end = off;
+    return o;
 }
+/* on chip the interval list and the pattern search's scratch (pattern_pack)
+ * lie on the sort buffer, free between the setup and each pack */
+static_assert(sw_plan_offsets<true>().sbuf + SW_BNB_BYTES <= sw_plan_offsets<true>().JL, "interval list");
+static_assert(sw_plan_offsets<true>().sbuf +
+                      4 * (SW_RCLS_MAX * (SW_TMAX + 1) + SW_PAT_SCRATCH(SW_LDS_JOBS)) <=
+                  sw_plan_offsets<true>().JL,
+              "pattern scratch");
+/* workspace path: both lie on the re-optimisation's rows, free until the end
+ * of P1 — the list on the first, the scratch (when it fits, solve_instance)
+ * on the two */
+static_assert(sw_plan_offsets<false>().rr_dpA + SW_BNB_BYTES <= sw_plan_offsets<false>().rr_dpB,
+              "interval list");
+constexpr int64_t SW_PSCR_LDS_WORDS = 2 * 2 * (SW_RR_CAPMAX + 1);
+static_assert(sw_plan_offsets<false>().rr_dpA + 4 * SW_PSCR_LDS_WORDS <= sw_plan_offsets<false>().rr_bits,
+              "pattern scratch");
+
+/* The level-search kernel: the setup's key staging window, whose space the
+ * level search's five per-job byte arrays and interval list reuse once the
+ * key rows are in registers, and the per-job constants. */
+struct sw_level_carve {
+    size_t X, bt, stage, JL, end;
+};
+__host__ __device__ constexpr sw_level_carve sw_level_offsets() {
+    sw_level_carve o{};
+    size_t off = 0;
+    o.X = off;     off += sw_r16(sizeof(sw_xchg));
+    o.bt = off;    off += sw_r16(sizeof(double) * 3 * SW_BMAX);
+    o.stage = off; off += sw_r16(SW_STAGE_BYTES);
+    o.JL = off;    off += sw_r16(sizeof(sw_job_soa));
+    o.end = off;
+    return o;
+}
+static_assert(sw_level_offsets().stage + 5 * SW_LDS_JOBS + SW_BNB_BYTES <= sw_level_offsets().JL,
+              "the staging window holds the level search's five per-job byte arrays and its interval list");
+/* the allocations the launches ask for: a change here changes how many
+ * workgroups share a CU */
+static_assert(sw_plan_offsets<true>().end == 141072 && sw_plan_offsets<false>().end == 46864 &&
+                  sw_level_offsets().end == 78976,
+              "dynamic LDS of the plan and level kernels");
 
 /* LDS of the pack kernel: pack and repair state, counts, masks, sort
  * exchange — the carve-up as constexpr offsets, shared by sw_pack_kernel and
@@ -1600,36 +1930,33 @@ struct sw_pack_carve {
     size_t X, PL, misc, rep, nbest, placed, placed2, ycur, y2, sbuf, end;
 };
 __host__ __device__ constexpr sw_pack_carve sw_pack_offsets() {
-    auto r16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
     const size_t NJ = SW_LDS_JOBS;
     sw_pack_carve o{};
     size_t off = 0;
-    o.X = off;       off += r16(sizeof(sw_xchg));
-    o.PL = off;      off += r16(sizeof(sw_pack_lds));
-    o.misc = off;    off += r16(sizeof(int64_t) * 8);
-    o.rep = off;     off += r16(sizeof(sw_repair_t));
-    o.nbest = off;   off += r16(NJ);
-    o.placed = off;  off += r16(NJ);
-    o.placed2 = off; off += r16(NJ);
-    o.ycur = off;    off += r16(8 * NJ);
-    o.y2 = off;      off += r16(8 * NJ);
-    o.sbuf = off;    off += r16(8 * 3 * SW_BLOCK); /* compaction + sort_one exchange */
+    o.X = off;       off += sw_r16(sizeof(sw_xchg));
+    o.PL = off;      off += sw_r16(sizeof(sw_pack_lds));
+    o.misc = off;    off += sw_r16(sizeof(int64_t) * 8);
+    o.rep = off;     off += sw_r16(sizeof(sw_repair_t));
+    o.nbest = off;   off += sw_r16(NJ);
+    o.placed = off;  off += sw_r16(NJ);
+    o.placed2 = off; off += sw_r16(NJ);
+    o.ycur = off;    off += sw_r16(8 * NJ);
+    o.y2 = off;      off += sw_r16(8 * NJ);
+    o.sbuf = off;    off += sw_r16(8 * 3 * SW_BLOCK); /* compaction + sort_one exchange */
     o.end = off;
     return o;
 }
-__host__ __device__ constexpr size_t sw_pack_lds_bytes() { return sw_pack_offsets().end; }
 
 /* LDS of the sort kernel (sw_sort_kernel): the front half's carve-outs only. */
 struct sw_sort_carve {
     size_t X, nbest, sbuf, end;
 };
 __host__ __device__ constexpr sw_sort_carve sw_sort_offsets() {
-    auto r16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
     sw_sort_carve o{};
     size_t off = 0;
-    o.X = off;     off += r16(sizeof(sw_xchg));
-    o.nbest = off; off += r16((size_t)SW_LDS_JOBS);
-    o.sbuf = off;  off += r16(8 * 3 * SW_BLOCK);
+    o.X = off;     off += sw_r16(sizeof(sw_xchg));
+    o.nbest = off; off += sw_r16((size_t)SW_LDS_JOBS);
+    o.sbuf = off;  off += sw_r16(8 * 3 * SW_BLOCK);
     o.end = off;
     return o;
 }
@@ -1644,48 +1971,14 @@ template <int KT>
 __device__ __forceinline__ void level_instance(const sw_batch_dev& B, unsigned char* smem, int inst_) {
     const sw_inst_dev* I = &B.inst[inst_];
     Ctx<KT, true> c;
-    c.inst = I;
-    c.N = I->N;
-    c.T = I->T;
-    c.G = I->G;
-    c.nb = I->nb;
-    c.C = (int64_t)I->G * I->T;
-    c.k = I->k;
-    c.inv_delta = 1.0 / I->delta;
-    c.passes = 0;
-    c.q = (c.N + SW_BLOCK - 1) / SW_BLOCK;
-    const int N = c.N;
+    c.init(B, I);
     const int64_t jo = I->job_off;
-    c.w_in = B.w + jo;
-    c.p_in = B.p + jo;
-#ifdef SW_STAMPS
-    c.swp = nullptr;
-    c.lsp = nullptr;
-#endif
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        unsigned char* p = smem + off;
-        off += (bytes + 15) & ~(size_t)15;
-        return p;
-    };
-    c.blk.X = (sw_xchg*)carve(sizeof(sw_xchg));
-    c.blk.par = 0;
-    double* bt = (double*)carve(sizeof(double) * 3 * SW_BMAX);
-    c.beta = bt;
-    c.ell = bt + SW_BMAX;
-    c.slope = bt + 2 * SW_BMAX;
-    if (threadIdx.x < SW_BMAX) {
-        const int b = (int)threadIdx.x;
-        bt[b] = I->beta[b];
-        bt[SW_BMAX + b] = I->ell[b];
-        bt[2 * SW_BMAX + b] = b < I->nb - 1 ? (I->ell[b + 1] - I->ell[b]) / (I->beta[b + 1] - I->beta[b])
-                                            : 0.0;
-    }
-    /* the setup's staging window; the level search's per-job bytes use the
-     * same space once the key rows are in registers */
-    unsigned char* stage = carve(sizeof(float) * SW_JPT * SW_SETUP_CH * SW_BLOCK);
-    static_assert(sizeof(float) * SW_JPT * SW_SETUP_CH * SW_BLOCK >= 5 * SW_LDS_JOBS,
-                  "the staging window holds the level search's five per-job byte arrays");
+    constexpr sw_level_carve O = sw_level_offsets();
+    c.blk.X = (sw_xchg*)(smem + O.X);
+    c.fill_pwl((double*)(smem + O.bt));
+    /* the setup's staging window; the level search's per-job bytes and its
+     * interval list use the same space once the key rows are in registers */
+    unsigned char* stage = smem + O.stage;
     c.sbuf = reinterpret_cast<uint64_t*>(stage);
     const int NJ = SW_LDS_JOBS;
     c.ncur = stage;
@@ -1693,28 +1986,8 @@ __device__ __forceinline__ void level_instance(const sw_batch_dev& B, unsigned c
     c.tkcur = stage + 2 * NJ;
     c.nbest = stage + 3 * NJ;
     c.tiecur = stage + 4 * NJ;
-    static_assert(sizeof(float) * SW_JPT * SW_SETUP_CH * SW_BLOCK >=
-                      5 * SW_LDS_JOBS + sizeof(sw_bnb_ivl) * SW_BNB_CAP,
-                  "the staging window also holds the level search's interval list");
     c.bnb = reinterpret_cast<sw_bnb_ivl*>(stage + 5 * NJ);
-    c.placed = c.placed2 = c.nfin = nullptr;
-    c.ycur = c.ybest = c.y2 = nullptr;
-    c.pst = nullptr;
-    c.pord = nullptr;
-    c.pmask = nullptr;
-    c.PL = nullptr;
-    c.H = c.SH = c.caps = nullptr;
-    c.pwc = 0;
-    c.misc = nullptr;
-    c.rep = nullptr;
-    c.gkeys = nullptr;
-    c.gjc = nullptr;
-    c.JL.carve(carve);
-    for (int j = threadIdx.x; j < NJ; j += SW_BLOCK)
-        c.JL.put(j, j < N ? sw_make_jobc(N, c.T, I->delta, B.w[jo + j], B.d[jo + j], B.F[jo + j],
-                                         B.E[jo + j], B.R[jo + j], B.p[jo + j])
-                          : sw_make_jobc(1, 1, 1.0, 1, 1.0, 0, 1, 0.0, 0.0));
-    if (off != sw_level_lds_bytes()) __builtin_trap();
+    c.fill_job_lds(B, smem + O.JL);
     __syncthreads();
     c.setup(); /* its closing barrier: the staging window is free */
     const double bound = c.level_search();
@@ -1734,7 +2007,10 @@ __device__ __forceinline__ void level_instance(const sw_batch_dev& B, unsigned c
 
 /* The 16-byte plan stores of the emit (shockwave.py:390-398 reads x[j][t]):
  * the instance's N·T-byte range written with aligned 16-byte stores, each
- * thread expanding 16 consecutive bytes from the round masks ym. */
+ * thread expanding 16 consecutive bytes from the round masks ym (a chunk
+ * spans at most ⌈16/T⌉ + 1 jobs), byte stores only for the unaligned head and
+ * tail — instead of every thread storing its own jobs' bytes one at a time
+ * (strided byte stores that inflated WRITE_SIZE by ~1.6x). */
 __device__ __forceinline__ void emit_plan_bytes(uint8_t* plan, const uint64_t* ym, int N, int T) {
     const int32_t nbytes = N * T;
     const int32_t mis = (int32_t)(reinterpret_cast<uintptr_t>(plan) & 15u);
@@ -1765,43 +2041,19 @@ __device__ __forceinline__ void emit_plan_bytes(uint8_t* plan, const uint64_t* y
     }
 }
 
-/* The scalar fields of an on-chip pack context (pack_instance, sw_sort_kernel);
- * the LDS pointers start null, each kernel sets the carve-outs it has. */
-template <class CTX>
-__device__ __forceinline__ void pack_ctx_scalars(CTX& c, const sw_batch_dev& B, const sw_inst_dev* I) {
-    c.inst = I;
-    c.N = I->N;
-    c.T = I->T;
-    c.G = I->G;
-    c.nb = I->nb;
-    c.C = (int64_t)I->G * I->T;
-    c.k = I->k;
-    c.inv_delta = 1.0 / I->delta;
-    c.passes = 0;
-    c.q = (c.N + SW_BLOCK - 1) / SW_BLOCK;
-    c.w_in = B.w + I->job_off;
-    c.p_in = B.p + I->job_off;
-#ifdef SW_STAMPS
-    c.swp = nullptr;
-    c.lsp = nullptr;
-#endif
-    c.blk.par = 0;
-    c.beta = c.ell = c.slope = nullptr;
-    c.PL = nullptr;
-    c.H = c.SH = c.caps = nullptr;
-    c.pwc = 0;
-    c.misc = nullptr;
-    c.rep = nullptr;
-    c.nbest = c.placed = c.placed2 = nullptr;
-    c.ncur = c.lcur = c.tkcur = c.nfin = c.tiecur = nullptr;
-    c.bnb = nullptr;
-    c.ycur = c.y2 = c.ybest = nullptr;
-    c.sbuf = nullptr;
-    c.pst = nullptr;
-    c.pord = nullptr;
-    c.pmask = nullptr;
-    c.gkeys = nullptr;
-    c.gjc = nullptr;
+/* The emit's result record (thread 0): objective U − k·M and the P1
+ * certificate bit from it and the bound. */
+__device__ __forceinline__ void emit_out(sw_out_dev* out, double U, double M, double k, double P2,
+                                         double bound, int64_t passes, int32_t status) {
+    sw_out_dev o;
+    o.objective = U - k * M;
+    o.utility = U;
+    o.makespan = M;
+    o.p2_objective = P2;
+    o.bound = bound;
+    o.iters = (int32_t)passes;
+    o.status = status | (sw_p1_uncertified(o.objective, bound) ? SW_STATUS_P1_UNCERTIFIED : 0);
+    *out = o;
 }
 
 /* The position word of the loop workspace (sw_batch_dev::lws): the packed
@@ -1829,16 +2081,13 @@ template <bool WS>
 __device__ __forceinline__ const uint64_t* pack_instance(const sw_batch_dev& B, unsigned char* smem, int inst_) {
     const sw_inst_dev* I = &B.inst[inst_];
     Ctx<32, true, true> c;
-    pack_ctx_scalars(c, B, I);
+    c.init(B, I);
     const sw_lvl_dev lv = B.lvl[inst_];
     c.passes = lv.passes;
     const int64_t jo = I->job_off;
     constexpr sw_pack_carve O = sw_pack_offsets();
     c.blk.X = (sw_xchg*)(smem + O.X);
-    c.PL = (sw_pack_lds*)(smem + O.PL);
-    c.H = c.PL->H[0];
-    c.SH = c.PL->SH[0];
-    c.caps = c.PL->H[1];
+    c.set_pack_lds(smem + O.PL);
     c.misc = (int64_t*)(smem + O.misc);
     c.rep = (sw_repair_t*)(smem + O.rep);
     c.nbest = smem + O.nbest;
@@ -1906,17 +2155,7 @@ __device__ __forceinline__ const uint64_t* pack_instance(const sw_batch_dev& B, 
         const uint64_t m = c.ycur[j];
         const int cnt = __popcll(m);
         any_l += (cnt > 0);
-        double term = 0.0;
-        if (cnt > 0) {
-            const int64_t Ssum = (int64_t)__popcll(m & 0xAAAAAAAAAAAAAAAAull) +
-                                 2 * (int64_t)__popcll(m & 0xCCCCCCCCCCCCCCCCull) +
-                                 4 * (int64_t)__popcll(m & 0xF0F0F0F0F0F0F0F0ull) +
-                                 8 * (int64_t)__popcll(m & 0xFF00FF00FF00FF00ull) +
-                                 16 * (int64_t)__popcll(m & 0xFFFF0000FFFF0000ull) +
-                                 32 * (int64_t)__popcll(m & 0xFFFFFFFF00000000ull);
-            term = ((double)Ssum / (double)cnt) * c.p_in[j];
-        }
-        p2 = p2 + term;
+        p2 = p2 + (cnt > 0 ? sw_p2_term(m, cnt, c.p_in[j]) : 0.0);
         B.planned[jo + j] = cnt;
     });
     const double P2 = c.blk.detsum(p2);
@@ -1924,17 +2163,7 @@ __device__ __forceinline__ const uint64_t* pack_instance(const sw_batch_dev& B, 
     if (any_n == 0) status |= SW_STATUS_NO_PLANNED;
     /* the result record first: the reduction's values die before the plan
      * bytes' loop instead of being spilled across it */
-    if (threadIdx.x == 0) {
-        sw_out_dev o;
-        o.objective = lv.U - c.k * lv.M;
-        o.utility = lv.U;
-        o.makespan = lv.M;
-        o.p2_objective = P2;
-        o.bound = lv.bound;
-        o.iters = (int32_t)c.passes;
-        o.status = status | (sw_p1_uncertified(o.objective, lv.bound) ? SW_STATUS_P1_UNCERTIFIED : 0);
-        *out = o;
-    }
+    if (threadIdx.x == 0) emit_out(out, lv.U, lv.M, c.k, P2, lv.bound, c.passes, status);
     return c.ycur; /* the plan bytes and masks: after the exchange step (pack_tail) */
 }
 
@@ -1965,7 +2194,7 @@ __device__ __forceinline__ void pack_tail(const sw_batch_dev& B, const uint64_t*
     for (int k = 0; k < 2; ++k) act += (j0 + k < j1 && ym[j0 + k] != 0ull) ? 1 : 0;
     const bool run = B.fuse_p2x && !(out->status & SW_STATUS_P2_FALLBACK);
     sw_p2x_lds* L = reinterpret_cast<sw_p2x_lds*>(smem);
-    const size_t Lsz = (sizeof(sw_p2x_lds) + 15) & ~(size_t)15;
+    const size_t Lsz = SW_P2X_VAR_OFF;
     unsigned char* var = smem + Lsz;
     /* ym is the pack's ycur (pack_instance): the scan below writes the step's
      * exchange words L->X while ym is still read */
@@ -1986,11 +2215,7 @@ __device__ __forceinline__ void pack_tail(const sw_batch_dev& B, const uint64_t*
                             var + vb >= reinterpret_cast<const unsigned char*>(ym + N);
         unsigned char* base = onchip ? var + vb : B.p2ws + (size_t)SW_P2X_ARR_BYTES * jo;
         const size_t n = onchip ? (size_t)A : (size_t)N;
-        sw_p2x_arrays X;
-        X.cc = reinterpret_cast<double*>(base);
-        X.cm = reinterpret_cast<uint64_t*>(X.cc + n);
-        X.cw = reinterpret_cast<int32_t*>(X.cm + n);
-        X.cj = X.cw + n;
+        const sw_p2x_arrays X = sw_p2x_view(base, n);
         for (int k = 0, a = a0; k < 2; ++k) {
             if (j0 + k >= j1) break;
             const uint64_t m = ym[j0 + k];
@@ -2029,14 +2254,7 @@ __device__ __forceinline__ void pack_tail(const sw_batch_dev& B, const uint64_t*
                 continue;
             }
             mf[k] = X.cm[a++];
-            const int cnt = __popcll(mf[k]);
-            const int64_t Ssum = (int64_t)__popcll(mf[k] & 0xAAAAAAAAAAAAAAAAull) +
-                                 2 * (int64_t)__popcll(mf[k] & 0xCCCCCCCCCCCCCCCCull) +
-                                 4 * (int64_t)__popcll(mf[k] & 0xF0F0F0F0F0F0F0F0ull) +
-                                 8 * (int64_t)__popcll(mf[k] & 0xFF00FF00FF00FF00ull) +
-                                 16 * (int64_t)__popcll(mf[k] & 0xFFFF0000FFFF0000ull) +
-                                 32 * (int64_t)__popcll(mf[k] & 0xFFFFFFFF00000000ull);
-            acc = acc + ((double)Ssum / (double)cnt) * B.p[jo + j];
+            acc = acc + sw_p2_term(mf[k], __popcll(mf[k]), B.p[jo + j]);
         }
         if (nc > 0) { /* the P2 objective of the final masks, summed like the emit's */
             const double P2 = blk.detsum(acc);
@@ -2095,6 +2313,41 @@ struct RREnv {
     }
 };
 
+/* twin: twin_reround_arrays — the best P1 plan re-optimised round by round
+ * (sw_rr_run).  Its scratch is the P1 level-search / packing state, dead
+ * here; on chip: items in the level-search bytes, values in registers, the
+ * knapsack rows in ycur / y2, take bits and item values in the sort buffer;
+ * otherwise workspace rows and the LDS rows rr_*.  Returns the rounds changed. */
+template <int KT, bool ONE>
+__device__ __forceinline__ int reround(Ctx<KT, ONE>& c, double* rr_dpA, double* rr_dpB, uint64_t* rr_bits) {
+    RREnv<KT, ONE> e(c);
+    e.N = c.N;
+    e.T = c.T;
+    e.G = c.G;
+    e.k = c.k;
+    e.S = c.placed;
+    e.Sb = c.placed2;
+    if constexpr (ONE) {
+        e.items = reinterpret_cast<uint32_t*>(c.ncur);
+        e.bits = c.sbuf;
+        e.iv = reinterpret_cast<double*>(c.sbuf + SW_RR_WORDS);
+        e.dpA = reinterpret_cast<double*>(c.ycur);
+        e.dpB = reinterpret_cast<double*>(c.y2);
+        e.gv = e.g0 = e.g1 = nullptr;
+    } else {
+        e.items = c.pst;
+        e.iv = reinterpret_cast<double*>(c.pord);
+        e.gv = reinterpret_cast<double*>(c.ycur);
+        e.g0 = reinterpret_cast<double*>(c.y2);
+        e.g1 = reinterpret_cast<double*>(c.pmask);
+        e.dpA = rr_dpA;
+        e.dpB = rr_dpB;
+        e.bits = rr_bits;
+    }
+    return sw_rr_run(e, c.passes);
+}
+
+/* twin: twin_plan_solve */
 template <int KT, bool ONE>
 __device__ __forceinline__ void solve_instance(const sw_batch_dev& B, unsigned char* smem,
                                                          int inst_) {
@@ -2104,80 +2357,41 @@ __device__ __forceinline__ void solve_instance(const sw_batch_dev& B, unsigned c
     const uint64_t rt0_ = __builtin_amdgcn_s_memrealtime();
 #endif
     Ctx<KT, ONE> c;
-    c.inst = I;
-    c.N = I->N;
-    c.T = I->T;
-    c.G = I->G;
-    c.nb = I->nb;
-    c.C = (int64_t)I->G * I->T;
-    c.k = I->k;
-    c.inv_delta = 1.0 / I->delta;
-    c.passes = 0;
-    c.q = (c.N + SW_BLOCK - 1) / SW_BLOCK;
+    c.init(B, I);
     const int N = c.N;
     const int64_t jo = I->job_off;
-    c.w_in = B.w + jo;
 #ifdef SW_STAMPS
     c.swp = B.stamps ? B.stamps + (size_t)inst_ * SW_STAMP_SLOTS + 8 : nullptr;
     c.lsp = B.stamps ? B.stamps + (size_t)inst_ * SW_STAMP_SLOTS + 16 : nullptr;
 #endif
-    c.p_in = B.p + jo;
-
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        unsigned char* p = smem + off;
-        off += (bytes + 15) & ~(size_t)15;
-        return p;
-    };
-    c.blk.X = (sw_xchg*)carve(sizeof(sw_xchg));
-    c.blk.par = 0;
-    double* bt = (double*)carve(sizeof(double) * 3 * SW_BMAX);
-    c.beta = bt;
-    c.ell = bt + SW_BMAX;
-    c.slope = bt + 2 * SW_BMAX;
-    c.PL = (sw_pack_lds*)carve(sizeof(sw_pack_lds));
-    c.H = c.PL->H[0];
-    c.SH = c.PL->SH[0];
-    c.caps = c.PL->H[1]; /* spare row of the pack LDS */
-    c.pwc = 0;
-    c.misc = (int64_t*)carve(sizeof(int64_t) * 8);
-    c.rep = (sw_repair_t*)carve(sizeof(sw_repair_t));
+    constexpr sw_plan_carve O = sw_plan_offsets<ONE>();
+    c.blk.X = (sw_xchg*)(smem + O.X);
+    c.fill_pwl((double*)(smem + O.bt));
+    c.set_pack_lds(smem + O.PL);
+    c.misc = (int64_t*)(smem + O.misc);
+    c.rep = (sw_repair_t*)(smem + O.rep);
     double *rr_dpA = nullptr, *rr_dpB = nullptr; /* !ONE: LDS for the re-optimisation */
     uint64_t* rr_bits = nullptr;
-    if (threadIdx.x < SW_BMAX) {
-        const int b = (int)threadIdx.x;
-        bt[b] = I->beta[b];
-        bt[SW_BMAX + b] = I->ell[b];
-        /* sw_pwl_slopes, one segment per thread (same IEEE division) */
-        bt[2 * SW_BMAX + b] = b < I->nb - 1 ? (I->ell[b + 1] - I->ell[b]) / (I->beta[b + 1] - I->beta[b])
-                                            : 0.0;
-    }
+    /* the pattern search's scratch (pattern_pack): ONE: the sort buffer; !ONE:
+     * the re-optimisation's LDS rows when they hold it, else the workspace rows
+     * from y2 on (dead while a P1 pack is decided: 4N + 192 words) */
+    int32_t* pscr;
     if constexpr (ONE) {
-        const int NJ = SW_LDS_JOBS;
-        c.ncur = carve(NJ);
-        c.lcur = carve(NJ);
-        c.tkcur = carve(NJ);
-        c.nbest = carve(NJ);
-        c.placed = carve(NJ);
-        c.placed2 = carve(NJ);
-        c.nfin = carve(NJ);
-        c.tiecur = carve(NJ);
-        c.pst = nullptr;
-        c.pord = nullptr;
-        c.pmask = nullptr;
-        c.ycur = (uint64_t*)carve(sizeof(uint64_t) * NJ);
-        c.ybest = (uint64_t*)carve(sizeof(uint64_t) * NJ);
-        c.y2 = (uint64_t*)carve(sizeof(uint64_t) * NJ);
-        c.sbuf = (uint64_t*)carve(sizeof(uint64_t) * 4 * SW_JPT * SW_BLOCK);
+        c.ncur = smem + O.ncur;
+        c.lcur = smem + O.lcur;
+        c.tkcur = smem + O.tkcur;
+        c.nbest = smem + O.nbest;
+        c.placed = smem + O.placed;
+        c.placed2 = smem + O.placed2;
+        c.nfin = smem + O.nfin;
+        c.tiecur = smem + O.tiecur;
+        c.ycur = (uint64_t*)(smem + O.ycur);
+        c.ybest = (uint64_t*)(smem + O.ybest);
+        c.y2 = (uint64_t*)(smem + O.y2);
+        c.sbuf = (uint64_t*)(smem + O.sbuf);
         c.bnb = reinterpret_cast<sw_bnb_ivl*>(c.sbuf); /* free between the setup and each pack */
-        c.gkeys = nullptr;
-        c.gjc = nullptr;
-        c.JL.carve(carve);
-        /* every slot < SW_LDS_JOBS holds a valid record (a dummy past N) */
-        for (int j = threadIdx.x; j < NJ; j += SW_BLOCK)
-            c.JL.put(j, j < N ? sw_make_jobc(N, c.T, I->delta, B.w[jo + j], B.d[jo + j], B.F[jo + j],
-                                             B.E[jo + j], B.R[jo + j], B.p[jo + j])
-                              : sw_make_jobc(1, 1, 1.0, 1, 1.0, 0, 1, 0.0, 0.0));
+        pscr = reinterpret_cast<int32_t*>(c.sbuf);
+        c.fill_job_lds(B, smem + O.JL);
     } else {
         uint8_t* u8 = B.ws.u8 + SW_WS_U8 * jo;
         c.ncur = u8 + 0 * (size_t)N;
@@ -2202,32 +2416,17 @@ __device__ __forceinline__ void solve_instance(const sw_batch_dev& B, unsigned c
         c.sbuf = B.ws.sort + 4 * jo;
         c.gkeys = B.ws.keys + (size_t)KT * jo;
         c.gjc = B.ws.jc + jo;
-        rr_dpA = (double*)carve(8 * (SW_RR_CAPMAX + 1));
-        rr_dpB = (double*)carve(8 * (SW_RR_CAPMAX + 1));
-        rr_bits = (uint64_t*)carve(8 * SW_RR_WORDS);
-        /* the re-optimisation's LDS is free until the end of P1 */
-        static_assert(8 * (SW_RR_CAPMAX + 1) >= sizeof(sw_bnb_ivl) * SW_BNB_CAP, "interval list");
-        c.bnb = reinterpret_cast<sw_bnb_ivl*>(rr_dpA);
+        rr_dpA = (double*)(smem + O.rr_dpA);
+        rr_dpB = (double*)(smem + O.rr_dpB);
+        rr_bits = (uint64_t*)(smem + O.rr_bits);
+        c.bnb = reinterpret_cast<sw_bnb_ivl*>(rr_dpA); /* free until the end of P1 */
+        const int64_t need = SW_RCLS_MAX * (SW_TMAX + 1) + SW_PAT_SCRATCH((int64_t)N);
+        pscr = need <= SW_PSCR_LDS_WORDS ? reinterpret_cast<int32_t*>(rr_dpA)
+                                         : reinterpret_cast<int32_t*>(c.y2);
         for (int j = c.jlo(); j < c.jhi(); ++j)
             c.gjc[j] = sw_make_jobc(N, c.T, I->delta, B.w[jo + j], B.d[jo + j], B.F[jo + j],
                                     B.E[jo + j], B.R[jo + j], B.p[jo + j]);
     }
-    /* the pattern search's scratch (pattern_pack): ONE: the sort buffer; !ONE:
-     * the re-optimisation's LDS rows when they hold it, else the workspace rows
-     * from y2 on (dead while a P1 pack is decided: 4N + 192 words) */
-    int32_t* pscr;
-    if constexpr (ONE) {
-        static_assert(8 * 4 * SW_JPT * SW_BLOCK >=
-                          4 * (SW_RCLS_MAX * (SW_TMAX + 1) + SW_PAT_SCRATCH(SW_LDS_JOBS)),
-                      "pattern scratch");
-        pscr = reinterpret_cast<int32_t*>(c.sbuf);
-    } else {
-        const int64_t need = SW_RCLS_MAX * (SW_TMAX + 1) + SW_PAT_SCRATCH((int64_t)N);
-        pscr = need <= 2 * 2 * (SW_RR_CAPMAX + 1) ? reinterpret_cast<int32_t*>(rr_dpA)
-                                                  : reinterpret_cast<int32_t*>(c.y2);
-    }
-    /* folds away when the carve-up matches the launch's allocation */
-    if (off != sw_plan_lds_bytes(ONE)) __builtin_trap();
     __syncthreads();
 
 #ifdef SW_STAMPS
@@ -2236,14 +2435,13 @@ __device__ __forceinline__ void solve_instance(const sw_batch_dev& B, unsigned c
     c.setup();
     SW_STAMP(0);
 
-    /* ---- P1: level search + packing with budget re-solve, then P2
-     *      (twin_plan_solve).  One pack call site: requests are
-     *      (mode 1: P1 order A, mode 3: P1 order B, mode 2: P2). ---- */
+    /* ---- P1: level search + packing with budget re-solve.  One pack call
+     *      site: requests are (mode 4: density order, mode 1: P1 order A,
+     *      mode 3: P1 order B). ---- */
     int32_t status = 0;
     double bound = 0.0, Jbest = 0.0, Jp = 0.0;
     int64_t deficit = 0;
     int it = 0, mode = 0; /* mode 0 = run the level search next */
-    bool ok2 = true;
     bool dens = false, dens_best = false; /* P1 placed by the density order */
     bool rep = false, rep_best = false;   /* ... after a width-profile repair */
     bool dskip_best = false; /* density failed on exactly the final counts */
@@ -2256,13 +2454,15 @@ __device__ __forceinline__ void solve_instance(const sw_batch_dev& B, unsigned c
             dens = false;
             rep = false;
         }
-        if (mode == 2) break; /* P2 below */
+        if (mode == 2) break; /* P1 is decided */
         uint8_t* pl = (mode == 3) ? c.placed2 : c.placed;
         uint64_t* yd = (mode == 3) ? c.y2 : c.ycur;
         c.pack(mode, c.nbest, yd, pl);
 #ifdef SW_STAMPS
         const uint64_t ev0_ = __builtin_amdgcn_s_memtime();
 #endif
+        /* plan_objective(pl) by hand: its loop also sums the deficit, whose
+         * reduction comes first */
         int64_t def_l = 0;
         double fs = 0.0, gm = 0.0;
         c.for_jobs([&](int j, int s) {
@@ -2281,17 +2481,10 @@ __device__ __forceinline__ void solve_instance(const sw_batch_dev& B, unsigned c
         if (mode == 4) { /* density order: also the P2 placement when it packs */
             /* stranded rounds: repair the width profile (sw_repair.h) */
             if (dfc != 0 && c.repair_pack(c.nbest, c.ycur, c.placed, c.y2, c.placed2)) {
-                fs = 0.0;
-                gm = 0.0;
-                c.for_jobs([&](int j, int s) {
+                Jo = c.plan_objective(c.placed, U, Mx, [&](int j, int) {
                     c.ycur[j] = c.y2[j];
                     c.placed[j] = c.placed2[j];
-                    fs = fs + c.fval(j, s, c.placed[j]);
-                    gm = sw_max(gm, c.gval(j, s, c.placed[j]));
                 });
-                c.blk.detsum_max(fs, gm, U, Mx);
-                Jo = U - c.k * Mx;
-                c.passes++;
                 dfc = 0;
                 rep = true;
             }
@@ -2314,15 +2507,7 @@ __device__ __forceinline__ void solve_instance(const sw_batch_dev& B, unsigned c
         /* no order places the counts: an exact class profile over round
          * patterns (twin: pattern_pack) — the counts as they are, no re-solve */
         if (deficit != 0 && c.pattern_pack(c.nbest, c.ycur, c.placed, pscr)) {
-            fs = 0.0;
-            gm = 0.0;
-            c.for_jobs([&](int j, int s) {
-                fs = fs + c.fval(j, s, c.placed[j]);
-                gm = sw_max(gm, c.gval(j, s, c.placed[j]));
-            });
-            c.blk.detsum_max(fs, gm, U, Mx);
-            Jp = U - c.k * Mx;
-            c.passes++;
+            Jp = c.plan_objective(c.placed, U, Mx);
             deficit = 0;
         }
         /* this repack iteration is complete */
@@ -2349,275 +2534,46 @@ __device__ __forceinline__ void solve_instance(const sw_batch_dev& B, unsigned c
         }
         __syncthreads();
     }
-    /* ---- fill of stranded capacity (twin: fill_stranded): a re-solved P1
-     *      can leave round capacity idle; add single rounds there, largest
-     *      utility gain first (sw_fill_key), one block max per round ---- */
+    /* a re-solved P1 can strand capacity: fill it, re-optimise it round by
+     * round and try raises (a changed plan is no longer a density pack, so
+     * P2 starts from (a) again) */
     if (status & SW_STATUS_P1_REPACKED) {
-        int32_t* load = c.caps; /* spare pack row, free until class-wise P2 */
-        if (threadIdx.x < 64) load[threadIdx.x] = 0;
-        __syncthreads();
-        c.for_jobs([&](int j, int s) {
-            const uint64_t m = c.ybest[j];
-            const int32_t w = c.jc(j, s).w;
-            for (int t = 0; t < c.T; ++t)
-                if ((m >> t) & 1ull) atomicAdd(&load[t], w);
-        });
-        __syncthreads();
-        int added = 0;
-        for (int step = 0; step < SW_FILL_MAX; ++step) {
-            uint64_t best = 0;
-            c.for_jobs([&](int j, int s) {
-                const int n = c.nfin[j];
-                if (n >= c.Tj(j, s)) return;
-                const uint64_t m = c.ybest[j];
-                const int32_t w = c.jc(j, s).w;
-                int tf = -1;
-                for (int t = 0; t < c.T; ++t)
-                    if (!((m >> t) & 1ull) && w <= c.G - load[t]) { tf = t; break; }
-                if (tf < 0) return;
-                const uint64_t key = sw_fill_key(c.fval(j, s, n + 1) - c.fval(j, s, n), j, tf);
-                best = key > best ? key : best;
-            });
-            best = c.blk.umax(best); /* its barrier: every thread has read load */
-            c.passes++;
-            if (best == 0) break;
-            const int jb = (int)sw_fill_job(best);
-            const int tb = sw_fill_round(best);
-            if (jb >= c.jlo() && jb < c.jhi()) {
-                c.ybest[jb] |= 1ull << tb;
-                c.nfin[jb] = (uint8_t)(c.nfin[jb] + 1);
-            }
-            if (threadIdx.x == 0) load[tb] += c.w_in[jb];
-            ++added;
-            __syncthreads();
-        }
-        if (added > 0) {
-            dens_best = false;
-            rep_best = false;
-            dskip_best = false;
-        }
-        /* ... and re-optimise it round by round (twin: twin_reround_arrays).
-         * Its scratch is the P1 level-search / packing state, dead here; on
-         * chip: items in the level-search bytes, values in registers, the
-         * knapsack rows in ycur / y2, take bits and item values in the sort
-         * buffer */
-        RREnv<KT, ONE> e(c);
-        e.N = c.N;
-        e.T = c.T;
-        e.G = c.G;
-        e.k = c.k;
-        e.S = c.placed;
-        e.Sb = c.placed2;
-        if constexpr (ONE) {
-            e.items = reinterpret_cast<uint32_t*>(c.ncur);
-            e.bits = c.sbuf;
-            e.iv = reinterpret_cast<double*>(c.sbuf + SW_RR_WORDS);
-            e.dpA = reinterpret_cast<double*>(c.ycur);
-            e.dpB = reinterpret_cast<double*>(c.y2);
-            e.gv = e.g0 = e.g1 = nullptr;
-        } else {
-            e.items = c.pst;
-            e.iv = reinterpret_cast<double*>(c.pord);
-            e.gv = reinterpret_cast<double*>(c.ycur);
-            e.g0 = reinterpret_cast<double*>(c.y2);
-            e.g1 = reinterpret_cast<double*>(c.pmask);
-            e.dpA = rr_dpA;
-            e.dpB = rr_dpB;
-            e.bits = rr_bits;
-        }
-        if (sw_rr_run(e, c.passes) > 0) {
-            dens_best = false;
-            rep_best = false;
-            dskip_best = false;
-        }
-        /* ... and try raises (twin: raise_counts; sw_arith.h SW_RAISE_ITERS):
-         * one job one more round, the whole plan re-placed by the pattern
-         * search.  The try's counts go to nbest, its placement to ycur /
-         * placed (dead here); every decision is a block reduction */
-        for (int rit = 0; rit < SW_RAISE_ITERS; ++rit) {
-            double fs = 0.0, gm = 0.0;
-            int64_t ld_l = 0;
-            c.for_jobs([&](int j, int s) {
-                fs = fs + c.fval(j, s, c.nfin[j]);
-                gm = sw_max(gm, c.gval(j, s, c.nfin[j]));
-                ld_l += (int64_t)c.jc(j, s).w * c.nfin[j];
-            });
-            double U, M;
-            c.blk.detsum_max(fs, gm, U, M);
-            const double J = U - c.k * M;
-            const int64_t load = c.blk.sum(ld_l);
-            int32_t i1l = 0x7FFFFFFF; /* the first job attaining M, and the others' max */
-            c.for_jobs([&](int j, int s) {
-                if (j < i1l && c.gval(j, s, c.nfin[j]) == M) i1l = j;
-            });
-            const int32_t i1 = c.blk.min32(i1l);
-            double m2l = 0.0;
-            c.for_jobs([&](int j, int s) {
-                if (j != i1) m2l = sw_max(m2l, c.gval(j, s, c.nfin[j]));
-            });
-            const double M2 = c.blk.dmax(m2l);
-            c.passes++;
-            int32_t tried[SW_RAISE_TRIES];
-            bool took = false;
-            for (int tr = 0; tr < SW_RAISE_TRIES && !took; ++tr) {
-                uint64_t kl = 0;
-                c.for_jobs([&](int j, int s) {
-                    const int n = c.nfin[j];
-                    if (n >= c.Tj(j, s)) return;
-                    for (int q = 0; q < tr; ++q)
-                        if (tried[q] == j) return;
-                    const double Mo = j == i1 ? M2 : M;
-                    const uint64_t key = sw_fill_key(sw_raise_gain(c.fval(j, s, n), c.fval(j, s, n + 1),
-                                                                   c.gval(j, s, n + 1), Mo, M, c.k),
-                                                     j, 0);
-                    kl = key > kl ? key : kl;
-                });
-                const uint64_t best = c.blk.umax(kl);
-                if (best == 0) break; /* uniform */
-                const int b = (int)sw_fill_job(best);
-                tried[tr] = b;
-                if (load + c.w_in[b] > (int64_t)c.G * c.T) continue;
-                /* pattern_pack rewrites the rows of the jobs with rounds; the
-                 * others' rows (scratch of the re-optimisation) are cleared, as
-                 * the twin's pattern_pack clears its output */
-                c.for_jobs([&](int j, int s) {
-                    (void)s;
-                    c.nbest[j] = (uint8_t)(c.nfin[j] + (j == b ? 1 : 0));
-                    c.ycur[j] = 0;
-                    c.placed[j] = 0;
-                });
-                if (!c.pattern_pack(c.nbest, c.ycur, c.placed, pscr)) continue; /* uniform */
-                double fs2 = 0.0, gm2 = 0.0;
-                c.for_jobs([&](int j, int s) {
-                    fs2 = fs2 + c.fval(j, s, c.placed[j]);
-                    gm2 = sw_max(gm2, c.gval(j, s, c.placed[j]));
-                });
-                double U2, Mb2;
-                c.blk.detsum_max(fs2, gm2, U2, Mb2);
-                if (U2 - c.k * Mb2 > J) {
-                    c.for_jobs([&](int j, int s) {
-                        (void)s;
-                        c.nfin[j] = c.placed[j];
-                        c.ybest[j] = c.ycur[j];
-                    });
-                    took = true;
-                }
-            }
-            __syncthreads();
-            if (!took) break;
+        int changed = c.fill_stranded();
+        changed += reround(c, rr_dpA, rr_dpB, rr_bits);
+        changed += c.raise_counts(pscr);
+        if (changed > 0) {
             dens_best = false;
             rep_best = false;
             dskip_best = false;
         }
     }
-    /* ---- P2 (twin: the P2 block): (a) density order, (b) weight order,
-     *      (c) class-wise inside the P1 profile — first that places every
-     *      round, else the P1 placement ---- */
-    auto p2_ok = [&]() {
-        int64_t bad_l = 0;
-        c.for_jobs([&](int j, int s) { (void)s; bad_l += (c.placed[j] != c.nfin[j]); });
-        return c.blk.sum(bad_l) == 0;
-    };
-    ok2 = false;
-    if (dens_best) { /* (a) is the P1 placement itself */
-        c.for_jobs([&](int j, int s) { (void)s; c.y2[j] = c.ybest[j]; });
-        ok2 = true;
-        if (rep_best) status |= SW_STATUS_P2_REPAIRED;
-    }
-    for (int att = 0; att < 2 && !ok2; ++att) {
-        if (att == 0 && dskip_best) continue;
-        c.pack(att == 0 ? 4 : 2, c.nfin, c.y2, c.placed);
-        ok2 = p2_ok();
-        if (!ok2 && att == 0) { /* (a') density with its width profile repaired */
-            ok2 = c.repair_pack(c.nfin, c.y2, c.placed, c.ycur, c.placed2);
-            if (ok2) {
-                c.for_jobs([&](int j, int s) { (void)s; c.y2[j] = c.ycur[j]; });
-                status |= SW_STATUS_P2_REPAIRED;
-            }
-        }
-        if (ok2 && att == 1) status |= SW_STATUS_P2_WEIGHT_ORDER;
-    }
-    if (!ok2) {
-        int32_t wprev = 0;
-        while (true) {
-            int32_t wl = 0x7FFFFFFF;
-            c.for_jobs([&](int j, int s) {
-                const int32_t w = c.jc(j, s).w;
-                if (c.nfin[j] > 0 && w > wprev && w < wl) wl = w;
-            });
-            const int32_t wc = c.blk.min32(wl);
-            if (wc == 0x7FFFFFFF) break;
-            __syncthreads(); /* the previous class's pack has read caps */
-            if (threadIdx.x < 64) c.caps[threadIdx.x] = 0;
-            __syncthreads();
-            c.for_jobs([&](int j, int s) {
-                if (c.nfin[j] > 0 && c.jc(j, s).w == wc) {
-                    const uint64_t m = c.ybest[j];
-                    for (int t = 0; t < c.T; ++t)
-                        if ((m >> t) & 1ull) atomicAdd(&c.caps[t], 1);
-                }
-            });
-            c.pwc = wc;
-            c.pack(5, c.nfin, c.y2, c.placed);
-            wprev = wc;
-        }
-        ok2 = p2_ok();
-        if (ok2) status |= SW_STATUS_P2_CLASSWISE;
-    }
+    const bool ok2 = c.place_p2(dens_best, rep_best, dskip_best, status);
     SW_STAMP(4);
     if (!ok2) status |= SW_STATUS_P2_FALLBACK;
 
     /* ---- emit ---- */
     int64_t any_l = 0;
     double fs = 0.0, gm = 0.0, p2 = 0.0;
-    const int T = c.T;
-    uint8_t* plan = B.plan + I->plan_off;
     c.for_jobs([&](int j, int s) {
         const uint64_t m = ok2 ? c.y2[j] : c.ybest[j];
         const int cnt = __popcll(m);
         any_l += (cnt > 0);
         fs = fs + c.fval(j, s, cnt);
         gm = sw_max(gm, c.gval(j, s, cnt));
-        double term = 0.0;
-        if (cnt > 0) {
-            /* Σ_t t·bit_t of the mask: bit b of t weighted 2^b, six popcounts */
-            const int64_t Ssum = (int64_t)__popcll(m & 0xAAAAAAAAAAAAAAAAull) +
-                                 2 * (int64_t)__popcll(m & 0xCCCCCCCCCCCCCCCCull) +
-                                 4 * (int64_t)__popcll(m & 0xF0F0F0F0F0F0F0F0ull) +
-                                 8 * (int64_t)__popcll(m & 0xFF00FF00FF00FF00ull) +
-                                 16 * (int64_t)__popcll(m & 0xFFFF0000FFFF0000ull) +
-                                 32 * (int64_t)__popcll(m & 0xFFFFFFFF00000000ull);
-            term = ((double)Ssum / (double)cnt) * c.p_in[j];
-        }
-        p2 = p2 + term;
+        p2 = p2 + (cnt > 0 ? sw_p2_term(m, cnt, c.p_in[j]) : 0.0);
         B.planned[jo + j] = cnt;
         B.masks[jo + j] = m; /* for the P2 exchange kernel (sw_p2x_kernel.hip) */
     });
-    /* the four emit results in one reduction; its barrier: every mask row
-     * is final */
+    /* plan_objective and the P2 sum in one reduction; its barrier: every
+     * mask row is final */
     double U, Mact, P2;
     int64_t any_n;
     c.blk.detsum2_max_cnt(fs, p2, gm, (int32_t)any_l, U, P2, Mact, any_n);
-    const bool any = any_n > 0;
-    if (!any) status |= SW_STATUS_NO_PLANNED;
-    /* The plan bytes (shockwave.py:390-398 reads x[j][t]) with aligned
-     * 16-byte stores, each thread expanding 16 consecutive bytes from the
-     * round masks (a chunk spans at most ⌈16/T⌉ + 1 jobs), byte stores only
-     * for the unaligned head and tail — instead of every thread storing its
-     * own jobs' bytes one at a time (strided byte stores that inflated
-     * WRITE_SIZE by ~1.6x). */
-    emit_plan_bytes(plan, ok2 ? c.y2 : c.ybest, N, T);
+    if (any_n == 0) status |= SW_STATUS_NO_PLANNED;
+    emit_plan_bytes(B.plan + I->plan_off, ok2 ? c.y2 : c.ybest, N, c.T);
     SW_STAMP(5);
     if (threadIdx.x == 0) {
-        sw_out_dev o;
-        o.objective = U - c.k * Mact;
-        o.utility = U;
-        o.makespan = Mact;
-        o.p2_objective = P2;
-        o.bound = bound;
-        o.iters = (int32_t)c.passes;
-        o.status = status | (sw_p1_uncertified(o.objective, bound) ? SW_STATUS_P1_UNCERTIFIED : 0);
-        B.out[inst_] = o;
+        emit_out(&B.out[inst_], U, Mact, c.k, P2, bound, c.passes, status);
 #ifdef SW_STAMPS
         if (B.stamps) {
             uint64_t* st = B.stamps + (size_t)inst_ * SW_STAMP_SLOTS;
@@ -2695,7 +2651,7 @@ __global__ __launch_bounds__(SW_BLOCK, 8) void sw_sort_kernel(sw_batch_dev B) {
     const int inst_ = blockIdx.x;
     const sw_inst_dev* I = &B.inst[inst_];
     Ctx<32, true, true> c;
-    pack_ctx_scalars(c, B, I);
+    c.init(B, I);
     const int64_t jo = I->job_off;
     constexpr sw_sort_carve O = sw_sort_offsets();
     c.blk.X = (sw_xchg*)(sw_smem + O.X);
@@ -2791,22 +2747,25 @@ __global__ __launch_bounds__(SW_BLOCK, 8) void sw_place_kernel(sw_batch_dev B) {
     if (ym) pack_tail(B, ym, sw_smem, blockIdx.x);
 }
 
-/* LDS bytes the kernel needs (solve_instance checks its carve-up against it). */
-extern "C" size_t sw_plan_kernel_lds_bytes(int one) { return sw_plan_lds_bytes(one != 0); }
+/* LDS of a full-kernel launch: its layout, and room for the fused exchange
+ * step of the batch's largest instance. */
+static size_t plan_launch_lds(bool one, bool fused, int maxN, int maxT) {
+    const size_t lds = one ? sw_plan_offsets<true>().end : sw_plan_offsets<false>().end;
+    return fused ? std::max(lds, sw_p2x_lds_bytes(maxN, maxT)) : lds;
+}
 
-/* The split path for on-chip batches (every instance N ≤ SW_LDS_JOBS and
- * T ≤ 32): level search, then pack + emit (sw_pack_kernel, or with
- * B->loop_split its sort / rounds / place kernels), then the full kernel for
- * the instances the pack stage marked (B->only_slow set by the caller). */
-/* Every instance's exchange step runs inside these launches: the pack
- * kernel's instances at its end, the marked ones at the end of the full
- * kernel (p2x_lds: the step's LDS for the batch's largest instance). */
-extern "C" hipError_t sw_launch_split(sw_batch_dev* B, size_t p2x_lds, hipStream_t stream) {
+/* The split path for on-chip batches (sw_on_chip(maxN, maxT)): level search,
+ * then pack + emit (sw_pack_kernel, or with B->loop_split its sort / rounds /
+ * place kernels), then the full kernel for the instances the pack stage
+ * marked.  Every instance's exchange step runs inside these launches: the
+ * pack kernel's instances at its end, the marked ones at the end of the full
+ * kernel. */
+extern "C" hipError_t sw_launch_split(sw_batch_dev* B, int maxN, int maxT, hipStream_t stream) {
     dim3 grid(B->count), block(SW_BLOCK);
     B->only_slow = 0;
     B->fuse_p2x = 1;
-    hipLaunchKernelGGL((sw_level_kernel<32>), grid, block, sw_level_lds_bytes(), stream, *B);
-    B->lds_bytes = (int32_t)std::max(sw_pack_lds_bytes(), p2x_lds);
+    hipLaunchKernelGGL((sw_level_kernel<32>), grid, block, sw_level_offsets().end, stream, *B);
+    B->lds_bytes = (int32_t)std::max(sw_pack_offsets().end, sw_p2x_lds_bytes(maxN, maxT));
     if (B->loop_split) {
         hipLaunchKernelGGL(sw_sort_kernel, grid, block, sw_sort_offsets().end, stream, *B);
         dim3 rgrid((B->count + SW_LOOP_WPB - 1) / SW_LOOP_WPB), rblock(64 * SW_LOOP_WPB);
@@ -2816,18 +2775,22 @@ extern "C" hipError_t sw_launch_split(sw_batch_dev* B, size_t p2x_lds, hipStream
         hipLaunchKernelGGL(sw_pack_kernel, grid, block, (size_t)B->lds_bytes, stream, *B);
     }
     B->only_slow = 1;
-    hipLaunchKernelGGL((sw_plan_kernel<32, true>), grid, block, std::max(sw_plan_lds_bytes(true), p2x_lds),
+    hipLaunchKernelGGL((sw_plan_kernel<32, true>), grid, block, plan_launch_lds(true, true, maxN, maxT),
                        stream, *B);
     B->only_slow = 0;
     return hipGetLastError();
 }
 
-extern "C" hipError_t sw_launch_plan(const sw_batch_dev* B, int KT, int one, size_t lds,
-                                     hipStream_t stream) {
+/* The full kernel for the whole batch (B->fuse_p2x: with each instance's
+ * exchange step at its end). */
+extern "C" hipError_t sw_launch_plan(const sw_batch_dev* B, int maxN, int maxT, hipStream_t stream) {
     dim3 grid(B->count), block(SW_BLOCK);
-    if (KT == 32) {
-        if (one) hipLaunchKernelGGL((sw_plan_kernel<32, true>), grid, block, lds, stream, *B);
-        else hipLaunchKernelGGL((sw_plan_kernel<32, false>), grid, block, lds, stream, *B);
+    const bool one = sw_on_chip(maxN, maxT);
+    const size_t lds = plan_launch_lds(one, B->fuse_p2x != 0, maxN, maxT);
+    if (one) {
+        hipLaunchKernelGGL((sw_plan_kernel<32, true>), grid, block, lds, stream, *B);
+    } else if (maxT <= 32) {
+        hipLaunchKernelGGL((sw_plan_kernel<32, false>), grid, block, lds, stream, *B);
     } else {
         /* T > 32: key rows live in the HBM workspace (a 4×64 register row
          * would not fit the on-chip budget) */

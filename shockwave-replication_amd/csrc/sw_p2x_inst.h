@@ -39,6 +39,24 @@ __device__ __forceinline__ int j1r(int N) {
     return min(sw_tid_opaque() * q + q, N);
 }
 
+/* LDS of the step: its fixed state, then (16-byte aligned) the variable part
+ * for instances up to maxN jobs and maxT rounds. */
+constexpr size_t SW_P2X_VAR_OFF = (sizeof(sw_p2x_lds) + 15) & ~(size_t)15;
+__host__ __device__ inline size_t sw_p2x_lds_bytes(int maxN, int maxT) {
+    return SW_P2X_VAR_OFF + sw_p2x_var_bytes(maxN, maxT);
+}
+
+/* The step's per-job arrays (sw_p2x_arrays) as n entries each from base
+ * (SW_P2X_ARR_BYTES per entry). */
+__device__ __forceinline__ sw_p2x_arrays sw_p2x_view(unsigned char* base, size_t n) {
+    sw_p2x_arrays X;
+    X.cc = reinterpret_cast<double*>(base);
+    X.cm = reinterpret_cast<uint64_t*>(X.cc + n);
+    X.cw = reinterpret_cast<int32_t*>(X.cm + n);
+    X.cj = X.cw + n;
+    return X;
+}
+
 __device__ __forceinline__ void sw_p2x_instance(const sw_batch_dev& B, unsigned char* ws,
                                                 unsigned char* smem, int inst) {
     const sw_inst_dev* I = &B.inst[inst];
@@ -47,19 +65,11 @@ __device__ __forceinline__ void sw_p2x_instance(const sw_batch_dev& B, unsigned 
     if (out->status & SW_STATUS_P2_FALLBACK) return; /* P1's x is kept as is (:325-326) */
     const int64_t jo = I->job_off;
     sw_p2x_lds* L = reinterpret_cast<sw_p2x_lds*>(smem);
-    unsigned char* var = smem + ((sizeof(sw_p2x_lds) + 15) & ~(size_t)15);
+    unsigned char* var = smem + SW_P2X_VAR_OFF;
     sw_blk blk;
     blk.X = &L->X;
     blk.par = 0;
-    sw_p2x_arrays X;
-    {
-        unsigned char* base = ws + (size_t)SW_P2X_ARR_BYTES * jo;
-        const size_t n = (size_t)N;
-        X.cc = reinterpret_cast<double*>(base);
-        X.cm = reinterpret_cast<uint64_t*>(X.cc + n);
-        X.cw = reinterpret_cast<int32_t*>(X.cm + n);
-        X.cj = X.cw + n;
-    }
+    const sw_p2x_arrays X = sw_p2x_view(ws + (size_t)SW_P2X_ARR_BYTES * jo, (size_t)N);
     /* compaction in job order: thread l takes jobs [l·q, (l+1)·q) (the
      * plan kernel's job split, so the P2 sum below has its lanes) */
     const int q = (N + SW_BLOCK - 1) / SW_BLOCK;
@@ -111,14 +121,7 @@ __device__ __forceinline__ void sw_p2x_instance(const sw_batch_dev& B, unsigned 
             B.masks[jo2 + j] = m;
             for (int t = 0; t < T; ++t) plan[(size_t)j * T + t] = (uint8_t)((m >> t) & 1ull);
         }
-        const int cnt = __popcll(m);
-        const int64_t Ssum = (int64_t)__popcll(m & 0xAAAAAAAAAAAAAAAAull) +
-                             2 * (int64_t)__popcll(m & 0xCCCCCCCCCCCCCCCCull) +
-                             4 * (int64_t)__popcll(m & 0xF0F0F0F0F0F0F0F0ull) +
-                             8 * (int64_t)__popcll(m & 0xFF00FF00FF00FF00ull) +
-                             16 * (int64_t)__popcll(m & 0xFFFF0000FFFF0000ull) +
-                             32 * (int64_t)__popcll(m & 0xFFFFFFFF00000000ull);
-        acc = acc + ((double)Ssum / (double)cnt) * B.p[jo2 + j];
+        acc = acc + sw_p2_term(m, __popcll(m), B.p[jo2 + j]);
     }
     const double P2 = blk.detsum(acc);
     if (threadIdx.x == 0) {

@@ -34,15 +34,9 @@ __global__ __launch_bounds__(SW_BLOCK, 8) void sw_p2x_kernel(sw_batch_dev B) {
     sw_p2x_instance(B, B.p2ws, smem, blockIdx.x);
 }
 
-/* LDS bytes of the batch kernel for instances up to maxN jobs, maxT rounds. */
-extern "C" size_t sw_p2x_kernel_lds_bytes(int maxN, int maxT) {
-    return ((sizeof(sw_p2x_lds) + 15) & ~(size_t)15) + sw_p2x_var_bytes(maxN, maxT);
-}
-
 extern "C" hipError_t sw_launch_p2x(const sw_batch_dev* B, int maxN, int maxT, hipStream_t stream) {
-    const size_t lds = sw_p2x_kernel_lds_bytes(maxN, maxT);
     dim3 grid(B->count), block(SW_BLOCK);
-    hipLaunchKernelGGL(sw_p2x_kernel, grid, block, lds, stream, *B);
+    hipLaunchKernelGGL(sw_p2x_kernel, grid, block, sw_p2x_lds_bytes(maxN, maxT), stream, *B);
     return hipGetLastError();
 }
 
