@@ -400,6 +400,58 @@ int sw_ftf_allocate_batch(sw_handle* h, int32_t count, const int64_t* offsets,
                           const double* full_time, const double* elapsed,
                           const double* isolated_time, double* allocation, double* levels);
 
+/*
+ * The Gavel water-filling MaxMinFairness allocation
+ * (policies/max_min_fairness_water_filling.py:303-409, selected as
+ * max_min_fairness_water_filling in utils.get_policy) for one worker type, or
+ * several with identical throughputs.  The reference raises every job that can
+ * still rise by a common amount c / (sf_j / w_j) (one ECOS LP per stage,
+ * :79-189, :363), freezes the jobs that cannot rise any more (one GLPK MILP per
+ * stage, :191-301, :388-398) and repeats, up to one stage per job.  Its fixed
+ * point is the lexicographic max-min allocation
+ *     x_j = min(1, L* / coefficients[j]),
+ *     L*  the largest level with Σ_j scale_factors[j]·min(1, L/coefficients[j])
+ *         ≤ num_workers,
+ * which this call computes in one kernel.  scale_factors[j] = job.scale_factor
+ * and coefficients[j] = scale_factor / priority_weight, in sorted job-id order
+ * (policy.py:14-33): the arguments of sw_mmf_allocate.  allocation (num_jobs
+ * doubles) receives x_j.  level (optional, 2 doubles) receives L* and the
+ * allocated capacity Σ_j scale_factors[j]·x_j (the kernel's deterministic
+ * sum).  When Σ_j scale_factors[j] ≤ num_workers every x_j is 1 and L* is the
+ * largest coefficient (the loop ends with every job at the bound x_j ≤ 1 of
+ * policy.py:57-63); otherwise L* is the largest double whose capacity sum is
+ * at most num_workers (the stage at which the capacity row of policy.py:57-63
+ * fills and the MILP finds no job that can still rise).  Unlike
+ * sw_mmf_allocate the result is unique and leaves no worker unallocated that
+ * a job could use.
+ * SW_ERR_INVALID: a scale factor outside [1, 255] (scale_factors_array,
+ * policy.py:14-26, feeds the capacity row); a coefficient that is not finite
+ * and > 0 (the reference maps a priority weight ≤ 0 to 0 and never raises
+ * that job, :336-345; the mirror rejects it); num_workers ≤ 0 (an empty
+ * cluster_spec has no allocation); null pointers with num_jobs > 0;
+ * num_jobs < 0.  Synchronous; num_jobs = 0 is a no-op that returns SW_OK with
+ * the level (0, 0) (policy.flatten returns None, :431-433, :493-495).
+ */
+int sw_wf_allocate(sw_handle* h, int32_t num_jobs, int32_t num_workers,
+                   const int32_t* scale_factors, const double* coefficients,
+                   double* allocation, double* level);
+
+/*
+ * count independent instances of sw_wf_allocate in one kernel launch (sweeps
+ * over cluster sizes and what-if states; the reference runs its stage loop
+ * once per state).  Instance i owns the jobs [offsets[i], offsets[i+1]) of the
+ * per-job arrays (CSR: count + 1 entries) and num_workers[i] workers.  levels
+ * (optional) is [count][2].  Every instance's result is bit for bit that of
+ * the single call; an empty instance is allowed and yields the level (0, 0).
+ * SW_ERR_INVALID: offsets[0] ≠ 0 or offsets that decrease; any
+ * num_workers[i] ≤ 0; the per-job cases of sw_wf_allocate; count < 0; null
+ * offsets or num_workers with count > 0; null per-job pointers with jobs
+ * present.  Synchronous; count = 0 is a no-op that returns SW_OK.
+ */
+int sw_wf_allocate_batch(sw_handle* h, int32_t count, const int64_t* offsets,
+                         const int32_t* num_workers, const int32_t* scale_factors,
+                         const double* coefficients, double* allocation, double* levels);
+
 #ifdef __cplusplus
 }
 #endif

@@ -129,6 +129,8 @@ struct sw_handle {
     void* mmf = nullptr;
     /* FinishTimeFairness allocation buffers (sw_ftf.hip) */
     void* ftf = nullptr;
+    /* water-filling MaxMinFairness allocation buffers (sw_wf.hip) */
+    void* wf = nullptr;
 };
 
 /* sw_shard.hip: frees the sharded-mode state and communicator */
@@ -137,4 +139,6 @@ void sw_shard_release(sw_handle* h);
 void sw_mmf_release(sw_handle* h);
 /* sw_ftf.hip: frees the FinishTimeFairness buffers */
 void sw_ftf_release(sw_handle* h);
+/* sw_wf.hip: frees the water-filling buffers */
+void sw_wf_release(sw_handle* h);
 

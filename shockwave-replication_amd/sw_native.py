@@ -318,6 +318,7 @@ EXPORTED_SYMBOLS = (
     "sw_dist_unique_id", "sw_dist_init", "sw_dist_plan_solve", "sw_dist_shard_range",
     "sw_dist_init_host", "sw_mmf_allocate", "sw_dist_plan_solve_dev", "sw_dist_enable_peer",
     "sw_mmf_allocate_types", "sw_batch_keep_masks", "sw_ftf_allocate", "sw_ftf_allocate_batch",
+    "sw_wf_allocate", "sw_wf_allocate_batch",
 )
 
 
@@ -398,6 +399,10 @@ def load(path: str | None = None):
     lib.sw_ftf_allocate_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _ip, _ip, _dp, _dp,
                                           _dp, _dp, _dp]
     lib.sw_ftf_allocate_batch.restype = C.c_int
+    lib.sw_wf_allocate.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip, _dp, _dp, _dp]
+    lib.sw_wf_allocate.restype = C.c_int
+    lib.sw_wf_allocate_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _ip, _ip, _dp, _dp, _dp]
+    lib.sw_wf_allocate_batch.restype = C.c_int
     if path is None:
         _LIB = lib
     return lib
@@ -586,6 +591,50 @@ class Solver:
                     "sw_ftf_allocate_batch")
         return [(x[off[i]:off[i + 1]].copy(), float(lvl[i, 0]), float(lvl[i, 1])) for i in range(count)]
 
+    # ---- Gavel water-filling MaxMinFairness allocation (include/shockwave_amd.h sw_wf_allocate) ----
+    @staticmethod
+    def _wf_arrays(scale_factors, coefficients):
+        sf = np.ascontiguousarray(scale_factors, dtype=np.int32)
+        c = np.ascontiguousarray(coefficients, dtype=np.float64)
+        if len(sf) != len(c):
+            raise ValueError("scale_factors and coefficients must have the same length")
+        return sf, c
+
+    def wf_allocate(self, scale_factors, coefficients, num_workers: int):
+        """x_j of the water-filling MaxMinFairness allocation (one worker type);
+        returns (x, L*, Σ sf_j·x_j)."""
+        sf, c = self._wf_arrays(scale_factors, coefficients)
+        x = np.zeros(len(sf), dtype=np.float64)
+        lvl = np.zeros(2, dtype=np.float64)
+        self._check(self.lib.sw_wf_allocate(self.h, len(sf), int(num_workers), sf.ctypes.data_as(_ip),
+                                            c.ctypes.data_as(_dp), x.ctypes.data_as(_dp),
+                                            lvl.ctypes.data_as(_dp)),
+                    "sw_wf_allocate")
+        return x, float(lvl[0]), float(lvl[1])
+
+    def wf_allocate_batch(self, instances, offsets=None):
+        """sw_wf_allocate_batch over a list of (scale_factors, coefficients,
+        num_workers) tuples, one kernel launch; returns the list of
+        (x, L*, Σ sf_j·x_j).  offsets (tests only) overrides the CSR offsets
+        built from the instances' lengths."""
+        parts = [self._wf_arrays(*inst[:2]) for inst in instances]
+        count = len(parts)
+        off = np.zeros(count + 1, dtype=np.int64)
+        for i, q in enumerate(parts):
+            off[i + 1] = off[i] + len(q[0])
+        sf, c = [np.ascontiguousarray(np.concatenate([q[k] for q in parts]) if parts else [], dtype=t)
+                 for k, t in enumerate((np.int32, np.float64))]
+        g = np.ascontiguousarray([int(inst[2]) for inst in instances], dtype=np.int32)
+        x = np.zeros(len(sf), dtype=np.float64)
+        lvl = np.zeros((count, 2), dtype=np.float64)
+        coff = off if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
+        self._check(self.lib.sw_wf_allocate_batch(self.h, count, coff.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                  g.ctypes.data_as(_ip), sf.ctypes.data_as(_ip),
+                                                  c.ctypes.data_as(_dp), x.ctypes.data_as(_dp),
+                                                  lvl.ctypes.data_as(_dp)),
+                    "sw_wf_allocate_batch")
+        return [(x[off[i]:off[i + 1]].copy(), float(lvl[i, 0]), float(lvl[i, 1])) for i in range(count)]
+
     # ---- sharded single instance (include/shockwave_amd.h sw_dist_*) ----
     def dist_init(self, unique_id: bytes, rank: int, world: int):
         """RCCL collectives; unique_id from unique_id() on rank 0, broadcast by the caller."""
@@ -637,6 +686,17 @@ class MmfAllocator:
 
     def __call__(self, scale_factors, coefficients, num_workers):
         return self.solver.mmf_allocate(scale_factors, coefficients, num_workers)[0]
+
+
+class WfAllocator:
+    """The simulator's water-filling MaxMinFairness allocation function on the
+    GPU: ``allocator(scale_factors, coefficients, num_workers) -> x``."""
+
+    def __init__(self, device=0, solver=None):
+        self.solver = solver or Solver(device=device)
+
+    def __call__(self, scale_factors, coefficients, num_workers):
+        return self.solver.wf_allocate(scale_factors, coefficients, num_workers)[0]
 
 
 def unique_id(lib=None) -> bytes:

@@ -4,8 +4,8 @@ Restates the part of the reference's ``Scheduler.simulate()``
 (scheduler/scheduler.py:1365-1796) that the Shockwave comparison runs:
 trace-driven arrivals, fixed-length rounds on a homogeneous v100 cluster,
 the Shockwave policy (plan solve on the GPU through ShockwaveScheduler) and
-the Gavel MaxMinFairness and FinishTimeFairness (Themis) baselines (allocation
-program + deficit-based priorities),
+the Gavel MaxMinFairness, water-filling MaxMinFairness and FinishTimeFairness
+(Themis) baselines (allocation program + deficit-based priorities),
 dynamic batch-size scaling (GNS / Accordion) and the Fig-9 metrics.
 
 What is kept from the reference, and where it lives:
@@ -30,6 +30,8 @@ The policy decisions go through pluggable objects so the same loop runs with
 the product solvers (HIP, default) or with the CPU oracles (tests only):
   * Shockwave: ``ShockwaveScheduler(config, solver=…)``;
   * MaxMinFairness: ``mmf_allocator(scale_factors, coefficients, G) → x``;
+  * MaxMinFairnessWaterFilling: ``wf_allocator(scale_factors, coefficients,
+    G) → x``, the same arguments;
   * FinishTimeFairness: ``ftf_allocator.ftf_allocate(scale_factors, full_time,
     elapsed, isolated_time, G) → (x, ρ*, μ)`` (the engine of the policy mirror
     finish_time_fairness.py).
@@ -55,26 +57,29 @@ MAX_FAILED_ATTEMPTS = 5  # scheduler.py:49
 WORKER_TYPE = "v100"  # the Shockwave hooks hard-code it (scheduler.py:1000, :3609)
 
 POLICY_NAMES = {"shockwave": "Shockwave", "max_min_fairness": "MaxMinFairness",
-                "finish_time_fairness": "FinishTimeFairness"}
+                "finish_time_fairness": "FinishTimeFairness",
+                "max_min_fairness_water_filling": "MaxMinFairnessWaterFilling"}
 
 
 class Simulator:
     """One simulated cluster run (the reference's ``Scheduler`` with
     ``simulate=True``).
 
-    policy:           "shockwave", "max_min_fairness" or "finish_time_fairness"
-                      (utils.get_policy names)
+    policy:           "shockwave", "max_min_fairness", "finish_time_fairness" or
+                      "max_min_fairness_water_filling" (utils.get_policy names)
     throughputs:      {(job_type, scale_factor): v100 steps/s} (sw_trace.load_throughputs)
     profiles:         {int job id: profile dict} (the trace pickle; sw_trace.synthesize_profiles)
     shockwave_config: the JSON config + time_per_iteration + num_gpus (driver :60-70)
     shockwave_solver: solver object for ShockwaveScheduler (default: the HIP solver)
     mmf_allocator:    MaxMinFairness allocation function (default: the HIP kernel)
     ftf_allocator:    FinishTimeFairness engine with ftf_allocate (default: the HIP solver)
+    wf_allocator:     water-filling allocation function (default: the HIP kernel)
     """
 
     def __init__(self, policy, throughputs, profiles, time_per_iteration=120,
                  shockwave_config=None, shockwave_solver=None, mmf_allocator=None,
-                 minimum_time_between_allocation_resets=1920, verbose=False, ftf_allocator=None):
+                 minimum_time_between_allocation_resets=1920, verbose=False, ftf_allocator=None,
+                 wf_allocator=None):
         if policy not in POLICY_NAMES:
             raise ValueError(f"Unknown policy {policy!r} (supported: {sorted(POLICY_NAMES)})")
         self.policy_name = POLICY_NAMES[policy]
@@ -123,6 +128,7 @@ class Simulator:
         self._mmf_allocator = mmf_allocator
         self._ftf_allocator = ftf_allocator
         self._ftf_policy = None
+        self._wf_allocator = wf_allocator
 
     # ---- helpers ------------------------------------------------------------------
     def _log(self, msg):
@@ -336,7 +342,10 @@ class Simulator:
         worker type: MaxMinFairnessPolicy replaces every throughput by 1.0, the
         proportional throughput of each job is then 1.0 (proportional.py:27-44),
         so the LP is  max min_j c_j x_j  s.t.  Σ_j sf_j x_j ≤ G, 0 ≤ x_j ≤ 1
-        with c_j = sf_j / priority_weight_j.  Jobs in sorted id order."""
+        with c_j = sf_j / priority_weight_j.  Jobs in sorted id order.
+        MaxMinFairnessWaterFilling (max_min_fairness_water_filling.py:412-468,
+        called with the same arguments, scheduler.py:2433-2436) takes the same
+        sf_j and c_j and returns x_j = min(1, L*/c_j)."""
         if self.policy_name == "FinishTimeFairness":
             return self._compute_ftf_allocation()
         ids = sorted(self._jobs.keys())
@@ -344,18 +353,26 @@ class Simulator:
             return {}
         sf = [self._jobs[j].scale_factor for j in ids]
         coef = [self._jobs[j].scale_factor / self._jobs[j].priority_weight for j in ids]
-        if self._mmf_allocator is None:
+        allocator = self._share_allocator()
+        import time
+        t0 = time.perf_counter()
+        x = allocator(sf, coef, len(self._worker_ids))
+        self.num_solves += 1
+        self.solve_seconds += time.perf_counter() - t0
+        return {j: min(1.0, max(0.0, float(v))) for j, v in zip(ids, x)}
+
+    def _share_allocator(self):
+        """The (scale_factors, coefficients, G) → x function of the policy; the
+        HIP kernel when none was injected."""
+        water_filling = self.policy_name == "MaxMinFairnessWaterFilling"
+        attr = "_wf_allocator" if water_filling else "_mmf_allocator"
+        if getattr(self, attr) is None:
             try:
                 from . import sw_native
             except ImportError:
                 import sw_native
-            self._mmf_allocator = sw_native.MmfAllocator()
-        import time
-        t0 = time.perf_counter()
-        x = self._mmf_allocator(sf, coef, len(self._worker_ids))
-        self.num_solves += 1
-        self.solve_seconds += time.perf_counter() - t0
-        return {j: min(1.0, max(0.0, float(v))) for j, v in zip(ids, x)}
+            setattr(self, attr, sw_native.WfAllocator() if water_filling else sw_native.MmfAllocator())
+        return getattr(self, attr)
 
     def _compute_ftf_allocation(self):
         """scheduler.py:2351-2428 → policies/finish_time_fairness.py:14-140: the
@@ -614,7 +631,7 @@ class Simulator:
 
 def run_trace(policy, trace_file, num_gpus, time_per_iteration=120, config=None,
               throughputs=None, shockwave_solver=None, mmf_allocator=None, max_jobs=None,
-              verbose=False, ftf_allocator=None):
+              verbose=False, ftf_allocator=None, wf_allocator=None):
     """The driver's main() (simulate_scheduler_with_trace.py:27-133): parse the
     trace, synthesise the profiles (the missing pickle), set job durations from
     them (:37-39), simulate, and return the Fig-9 metrics."""
@@ -632,6 +649,7 @@ def run_trace(policy, trace_file, num_gpus, time_per_iteration=120, config=None,
         sw_config["num_gpus"] = num_gpus
     sim = Simulator(policy, tp, profiles, time_per_iteration=time_per_iteration,
                     shockwave_config=sw_config, shockwave_solver=shockwave_solver,
-                    mmf_allocator=mmf_allocator, verbose=verbose, ftf_allocator=ftf_allocator)
+                    mmf_allocator=mmf_allocator, verbose=verbose, ftf_allocator=ftf_allocator,
+                    wf_allocator=wf_allocator)
     sim.simulate(num_gpus, arrivals, jobs)
     return sim.summary()

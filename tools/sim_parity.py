@@ -46,7 +46,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=64)
     ap.add_argument("--solver", choices=["gpu", "twin", "milp"], default="gpu")
     ap.add_argument("--policies", default="shockwave,max_min_fairness",
-                    help="comma-separated: shockwave, max_min_fairness, finish_time_fairness")
+                    help="comma-separated: shockwave, max_min_fairness, finish_time_fairness, "
+                         "max_min_fairness_water_filling")
     ap.add_argument("--max-jobs", type=int, default=None)
     ap.add_argument("--time-per-iteration", type=int, default=120)
     ap.add_argument("--future-rounds", type=int, default=None,
@@ -63,12 +64,15 @@ def main():
         solver = sn.Solver(device=0)
         mmf = sn.MmfAllocator(solver=solver)
         ftf = solver
+        wf = sn.WfAllocator(solver=solver)
     else:
         import mmf_ref
         mmf = mmf_ref.twin_allocator
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import ftf_ref
         ftf = ftf_ref.TwinEngine()
+        import wf_ref
+        wf = wf_ref.twin_allocator
         if a.solver == "twin":
             solver = twin_solver()
         else:
@@ -82,7 +86,7 @@ def main():
         with contextlib.redirect_stdout(io.StringIO()):
             r = sw_sim.run_trace(pol, trace, a.gpus, a.time_per_iteration, cfg,
                                  shockwave_solver=solver, mmf_allocator=mmf,
-                                 max_jobs=a.max_jobs, ftf_allocator=ftf)
+                                 max_jobs=a.max_jobs, ftf_allocator=ftf, wf_allocator=wf)
         r["wall_s"] = time.time() - t0
         out["runs"][pol] = r
         print(pol, json.dumps(r), flush=True)
