@@ -175,15 +175,12 @@ static void cancel(p2x_t* X, int32_t F, const int32_t* cyc, int32_t len, int32_t
     }
 }
 
-/*
- * The exchange step on the active jobs (ascending job order): job[i], w[i],
- * c[i] = p/n, m[i] (round mask, improved in place).  Returns the number of
- * cycles cancelled; 0 (no change) when there are more than SW_P2X_KMAX
- * width classes.
- */
-int32_t twin_p2x_run(int32_t A, int32_t T, int32_t G, const int32_t* job, const int32_t* w,
-                     const double* c, uint64_t* m) {
-    if (A <= 0 || T < 2 || A > SW_P2X_AMAX) return 0;
+/* The step's set-up: classes, positions, rank bitsets, free capacity and δ.
+ * NULL when the step is skipped (no jobs, T < 2, more than SW_P2X_AMAX jobs
+ * or more than SW_P2X_KMAX width classes). */
+static p2x_t* p2x_open(int32_t A, int32_t T, int32_t G, const int32_t* job, const int32_t* w,
+                       const double* c, const uint64_t* m, double* delta) {
+    if (A <= 0 || T < 2 || A > SW_P2X_AMAX) return NULL;
     p2x_t* X = (p2x_t*)calloc(1, sizeof(p2x_t));
     X->T = T;
     X->G = G;
@@ -191,7 +188,7 @@ int32_t twin_p2x_run(int32_t A, int32_t T, int32_t G, const int32_t* job, const 
         int32_t k = 0;
         while (k < X->K && X->wc[k] != w[i]) ++k;
         if (k == X->K) {
-            if (X->K == SW_P2X_KMAX) { free(X); return 0; }
+            if (X->K == SW_P2X_KMAX) { free(X); return NULL; }
             X->wc[X->K++] = w[i];
         }
     }
@@ -247,7 +244,26 @@ int32_t twin_p2x_run(int32_t A, int32_t T, int32_t G, const int32_t* job, const 
                 }
             v[q] = X->pc[q] * (double)S;
         }
-    const double delta = sw_p2x_delta(twin_detsum(v, A), T, A);
+    *delta = sw_p2x_delta(twin_detsum(v, A), T, A);
+    free(v); free(e);
+    return X;
+}
+
+static void p2x_close(p2x_t* X) {
+    free(X->pjob); free(X->pc); free(X->pm); free(X->B); free(X);
+}
+
+/*
+ * The exchange step on the active jobs (ascending job order): job[i], w[i],
+ * c[i] = p/n, m[i] (round mask, improved in place).  Returns the number of
+ * cycles cancelled; 0 (no change) when there are more than SW_P2X_KMAX
+ * width classes.
+ */
+int32_t twin_p2x_run(int32_t A, int32_t T, int32_t G, const int32_t* job, const int32_t* w,
+                     const double* c, uint64_t* m) {
+    double delta;
+    p2x_t* X = p2x_open(A, T, G, job, w, c, m, &delta);
+    if (!X) return 0;
     int32_t cyc[SW_TMAX + 1];
     int32_t* tmp = (int32_t*)malloc(sizeof(int32_t) * 2 * (size_t)SW_P2X_MAX_MOVES);
     int32_t ncancel = 0;
@@ -294,9 +310,41 @@ int32_t twin_p2x_run(int32_t A, int32_t T, int32_t G, const int32_t* job, const 
         }
         m[lo] = X->pm[q];
     }
-    free(tmp); free(v); free(e);
-    free(X->pjob); free(X->pc); free(X->pm); free(X->B); free(X);
+    free(tmp);
+    p2x_close(X);
     return ncancel;
+}
+
+/* ---- entry points for the step's own tests (tests/test_p2x.py) ---- */
+
+/* find_cycle on a given graph: W[T·T] (δ included, SW_P2X_NONE = no edge),
+ * room[T] against load size F, dw[T + 1] the warm distances in and the last
+ * distances out.  Returns the cycle's length, its nodes in cyc[T + 1]. */
+int32_t twin_p2x_find_cycle(int32_t T, int32_t F, const double* W, const int32_t* room, double* dw,
+                            int32_t warm, int32_t* cyc) {
+    if (T < 2 || T > SW_TMAX) return -1;
+    p2x_t* X = (p2x_t*)calloc(1, sizeof(p2x_t));
+    X->T = T;
+    memcpy(X->W, W, sizeof(double) * (size_t)T * T);
+    memcpy(X->room, room, sizeof(int32_t) * (size_t)T);
+    const int32_t len = find_cycle(X, F, cyc, dw, warm != 0);
+    free(X);
+    return len;
+}
+
+/* The set-up of twin_p2x_run on a placement and one build_w for load size F:
+ * W[T·T] (δ included) and Wk[T·T] out.  Returns δ; -1 when the step is
+ * skipped (W, Wk untouched). */
+double twin_p2x_edges(int32_t A, int32_t T, int32_t G, const int32_t* job, const int32_t* w,
+                      const double* c, const uint64_t* m, int32_t F, double* W, int8_t* Wk) {
+    double delta;
+    p2x_t* X = p2x_open(A, T, G, job, w, c, m, &delta);
+    if (!X) return -1.0;
+    build_w(X, F, delta);
+    memcpy(W, X->W, sizeof(double) * (size_t)T * T);
+    memcpy(Wk, X->Wk, (size_t)T * T);
+    p2x_close(X);
+    return delta;
 }
 
 /* The step on a full plan (y: [N][T] bytes, counts n): used by the plan twin. */

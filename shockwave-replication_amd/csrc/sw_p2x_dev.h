@@ -148,15 +148,17 @@ static __device__ __forceinline__ void p2x_find_cycle(sw_p2x_lds* L, const doubl
 #endif
         BF_STAMP(10);
         {
-            /* W[t][t] and missing edges are SW_P2X_NONE and every distance is
-             * ≤ 0, so they never win: no per-edge tests */
+            /* W[t][t] and missing edges are SW_P2X_NONE; an entry at or above
+             * it is no edge (the twin's !(w < SW_P2X_NONE)), whatever the
+             * distances: they can lie below −SW_P2X_NONE */
             const int ul = act ? lane : 0;
             const int t0 = wv * nq, t1 = min(T, t0 + nq);
             double cb = SW_P2X_NONE;
             int ct = 0;
             for (int t = t0; t < t1; ++t) {
-                const double v = L->bd[t] + W[t * T + ul];
-                const bool take = v < cb;
+                const double w = W[t * T + ul];
+                const double v = L->bd[t] + w;
+                const bool take = w < SW_P2X_NONE && v < cb;
                 cb = take ? v : cb;
                 ct = take ? t : ct;
             }
@@ -525,13 +527,40 @@ static __device__ __forceinline__ void p2x_sort_regs(uint64_t (&hi)[EMAX], uint6
     }
 }
 
+/* The set-up's state besides sw_p2x_lds, as sw_p2x_block's SETUP_ONLY form
+ * hands it out: the class count, the LDS carve-up of var and δ. */
+struct sw_p2x_state {
+    int K;
+    double* pc;   /* c by position                  */
+    int32_t* ord; /* position → a                   */
+    uint64_t* B;  /* rank bitsets, word-major       */
+    double* W;    /* [T][T] edge costs, δ included  */
+    int8_t* Wk;   /* [T][T] the edge's class        */
+    double delta;
+};
+
+/* L->fq for load size F: F / w_k for the classes that can carry F, 0 for the
+ * others.  The caller's barrier publishes it. */
+static __device__ __forceinline__ void p2x_load_size(sw_p2x_lds* L, int K, int F) {
+    const int tid = threadIdx.x;
+    if (tid < SW_P2X_KMAX) {
+        const int wk = tid < K ? L->wc[tid] : 0;
+        L->fq[tid] = (wk > 0 && wk <= F && F % wk == 0 && F / wk <= SW_P2X_QMAX) ? F / wk : 0;
+    }
+}
+
 /* EMAX: entries per thread the rank sort may hold in registers (the sharded
  * engine's single-workgroup step, up to SW_P2X_AMAX positions, uses 8; the
- * batch kernel, capped at 64 VGPRs, 1 and an LDS network above 512) */
-template <int NW, int EMAX = 1>
+ * batch kernel, capped at 64 VGPRs, 1 and an LDS network above 512).
+ * SETUP_ONLY (tests/native/p2x_probe.hip, never the product): stop after the
+ * set-up — classes, positions, rank bitsets, free capacity, δ — and hand its
+ * state to the caller in *st; returns 1, or 0 when the step is skipped.  The
+ * product's instantiations compile the body below without that branch. */
+template <int NW, int EMAX = 1, bool SETUP_ONLY = false>
 __device__ __forceinline__ int sw_p2x_block(sw_blk_t<NW>& blk, sw_p2x_lds* L, unsigned char* var,
                                             const sw_p2x_arrays& X, int A, int T, int G,
-                                            uint64_t* sp = nullptr, const sw_p2x_pre* pre = nullptr) {
+                                            uint64_t* sp = nullptr, const sw_p2x_pre* pre = nullptr,
+                                            sw_p2x_state* st = nullptr) {
     constexpr int NT = NW * 64;
     const int tid = threadIdx.x;
     (void)sp;
@@ -788,6 +817,16 @@ __device__ __forceinline__ int sw_p2x_block(sw_blk_t<NW>& blk, sw_p2x_lds* L, un
     __syncthreads();
     const double delta = L->delta;
     P2X_STAMP(2);
+    if constexpr (SETUP_ONLY) {
+        st->K = K;
+        st->pc = pc;
+        st->ord = ord;
+        st->B = B;
+        st->W = W;
+        st->Wk = Wk;
+        st->delta = delta;
+        return 1;
+    }
     /* ---- cancelling ---- */
     int ncancel = 0;
     /* cert[k]: the cancel count when load size k last had no cycle — while
@@ -806,10 +845,7 @@ __device__ __forceinline__ int sw_p2x_block(sw_blk_t<NW>& blk, sw_p2x_lds* L, un
 #pragma unroll
             for (int k = 0; k < SW_P2X_KMAX; ++k) certk = k == ki ? cert[k] : certk;
             if (certk == ncancel) continue; /* uniform */
-            if (tid < SW_P2X_KMAX) {
-                const int wk = tid < K ? L->wc[tid] : 0;
-                L->fq[tid] = (wk > 0 && wk <= F && F % wk == 0 && F / wk <= SW_P2X_QMAX) ? F / wk : 0;
-            }
+            p2x_load_size(L, K, F);
             __syncthreads();
             bool all = true;
             while (ncancel < SW_P2X_MAX_CANCEL) {
