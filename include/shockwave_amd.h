@@ -452,6 +452,46 @@ int sw_wf_allocate_batch(sw_handle* h, int32_t count, const int64_t* offsets,
                          const int32_t* num_workers, const int32_t* scale_factors,
                          const double* coefficients, double* allocation, double* levels);
 
+/*
+ * The Gavel MinTotalDuration (makespan) baseline's allocation
+ * (policies/min_total_duration.py:41-106, selected as min_total_duration in
+ * utils.get_policy) for one worker type, or several with identical
+ * throughputs.  The reference bisects T over [100, 1e6] (then a decade at a
+ * time above 1e6) to within 5 %, solving at every probe the feasibility LP
+ *     Σ_j scale_factor_j·x_j ≤ num_workers,  0 ≤ x_j ≤ 1,
+ *     throughput_j·x_j ≥ steps_j / T,
+ * and returns the x of the last feasible probe.  With full_time_j = steps
+ * remaining / throughput (≥ 0; 0 for a job with no steps left) a probe is
+ * feasible exactly when max_j full_time_j ≤ T and
+ * Σ_j scale_factor_j·full_time_j/T ≤ num_workers; this call runs the
+ * reference's probe sequence on that predicate in one kernel.  allocation
+ * (num_jobs doubles) receives a point of the feasible face at the found T,
+ * full_time_j/T ≤ x_j ≤ 1: its analytic centre under the barrier of
+ * sw_mmf_allocate, or x_j = full_time_j/T where the capacity row is tight
+ * and the face is that single point.  Which point the reference's ECOS
+ * returns is not pinned (ECOS is absent; the objective is a constant).  level
+ * (optional, 2 doubles) receives T and the capacity multiplier μ (0 at the
+ * single point).  A scale factor outside [1, 255], a full_time that is not
+ * finite, < 0 or > 1e15, or num_workers ≤ 0 are SW_ERR_INVALID.  Synchronous;
+ * num_jobs = 0 is a no-op with the level (0, 0) (policy.flatten returns None).
+ */
+int sw_mtd_allocate(sw_handle* h, int32_t num_jobs, int32_t num_workers,
+                    const int32_t* scale_factors, const double* full_time,
+                    double* allocation, double* level);
+
+/*
+ * count independent instances of sw_mtd_allocate in one kernel launch (sweeps
+ * over cluster sizes and what-if states).  Instance i owns the jobs
+ * [offsets[i], offsets[i+1]) of the per-job arrays (CSR: count + 1 entries,
+ * offsets[0] = 0, never decreasing; an empty instance is allowed and yields
+ * the level (0, 0)) and num_workers[i] workers.  levels (optional) is
+ * [count][2].  Every instance's result is bit for bit that of the single
+ * call.  Synchronous; count = 0 is a no-op.
+ */
+int sw_mtd_allocate_batch(sw_handle* h, int32_t count, const int64_t* offsets,
+                          const int32_t* num_workers, const int32_t* scale_factors,
+                          const double* full_time, double* allocation, double* levels);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,8 @@ struct sw_handle {
     void* ftf = nullptr;
     /* water-filling MaxMinFairness allocation buffers (sw_wf.hip) */
     void* wf = nullptr;
+    /* MinTotalDuration allocation buffers (sw_mtd.hip) */
+    void* mtd = nullptr;
 };
 
 /* sw_shard.hip: frees the sharded-mode state and communicator */
@@ -141,4 +143,6 @@ void sw_mmf_release(sw_handle* h);
 void sw_ftf_release(sw_handle* h);
 /* sw_wf.hip: frees the water-filling buffers */
 void sw_wf_release(sw_handle* h);
+/* sw_mtd.hip: frees the MinTotalDuration buffers */
+void sw_mtd_release(sw_handle* h);
 

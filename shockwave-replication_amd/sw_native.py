@@ -318,7 +318,7 @@ EXPORTED_SYMBOLS = (
     "sw_dist_unique_id", "sw_dist_init", "sw_dist_plan_solve", "sw_dist_shard_range",
     "sw_dist_init_host", "sw_mmf_allocate", "sw_dist_plan_solve_dev", "sw_dist_enable_peer",
     "sw_mmf_allocate_types", "sw_batch_keep_masks", "sw_ftf_allocate", "sw_ftf_allocate_batch",
-    "sw_wf_allocate", "sw_wf_allocate_batch",
+    "sw_wf_allocate", "sw_wf_allocate_batch", "sw_mtd_allocate", "sw_mtd_allocate_batch",
 )
 
 
@@ -403,6 +403,10 @@ def load(path: str | None = None):
     lib.sw_wf_allocate.restype = C.c_int
     lib.sw_wf_allocate_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _ip, _ip, _dp, _dp, _dp]
     lib.sw_wf_allocate_batch.restype = C.c_int
+    lib.sw_mtd_allocate.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip, _dp, _dp, _dp]
+    lib.sw_mtd_allocate.restype = C.c_int
+    lib.sw_mtd_allocate_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _ip, _ip, _dp, _dp, _dp]
+    lib.sw_mtd_allocate_batch.restype = C.c_int
     if path is None:
         _LIB = lib
     return lib
@@ -633,6 +637,49 @@ class Solver:
                                                   c.ctypes.data_as(_dp), x.ctypes.data_as(_dp),
                                                   lvl.ctypes.data_as(_dp)),
                     "sw_wf_allocate_batch")
+        return [(x[off[i]:off[i + 1]].copy(), float(lvl[i, 0]), float(lvl[i, 1])) for i in range(count)]
+
+    # ---- Gavel MinTotalDuration allocation (include/shockwave_amd.h sw_mtd_allocate) ----
+    @staticmethod
+    def _mtd_arrays(scale_factors, full_time):
+        sf = np.ascontiguousarray(scale_factors, dtype=np.int32)
+        p = np.ascontiguousarray(full_time, dtype=np.float64)
+        if len(sf) != len(p):
+            raise ValueError("scale_factors and full_time must have the same length")
+        return sf, p
+
+    def mtd_allocate(self, scale_factors, full_time, num_workers: int):
+        """x_j of the MinTotalDuration allocation (one worker type); returns (x, T, μ)."""
+        sf, p = self._mtd_arrays(scale_factors, full_time)
+        x = np.zeros(len(sf), dtype=np.float64)
+        lvl = np.zeros(2, dtype=np.float64)
+        self._check(self.lib.sw_mtd_allocate(self.h, len(sf), int(num_workers), sf.ctypes.data_as(_ip),
+                                             p.ctypes.data_as(_dp), x.ctypes.data_as(_dp),
+                                             lvl.ctypes.data_as(_dp)),
+                    "sw_mtd_allocate")
+        return x, float(lvl[0]), float(lvl[1])
+
+    def mtd_allocate_batch(self, instances, offsets=None):
+        """sw_mtd_allocate_batch over a list of (scale_factors, full_time,
+        num_workers) tuples, one kernel launch; returns the list of (x, T, μ).
+        offsets (tests only) overrides the CSR offsets built from the
+        instances' lengths."""
+        parts = [self._mtd_arrays(*inst[:2]) for inst in instances]
+        count = len(parts)
+        off = np.zeros(count + 1, dtype=np.int64)
+        for i, q in enumerate(parts):
+            off[i + 1] = off[i] + len(q[0])
+        sf, p = [np.ascontiguousarray(np.concatenate([q[k] for q in parts]) if parts else [], dtype=t)
+                 for k, t in enumerate((np.int32, np.float64))]
+        g = np.ascontiguousarray([int(inst[2]) for inst in instances], dtype=np.int32)
+        x = np.zeros(len(sf), dtype=np.float64)
+        lvl = np.zeros((count, 2), dtype=np.float64)
+        coff = off if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
+        self._check(self.lib.sw_mtd_allocate_batch(self.h, count, coff.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                   g.ctypes.data_as(_ip), sf.ctypes.data_as(_ip),
+                                                   p.ctypes.data_as(_dp), x.ctypes.data_as(_dp),
+                                                   lvl.ctypes.data_as(_dp)),
+                    "sw_mtd_allocate_batch")
         return [(x[off[i]:off[i + 1]].copy(), float(lvl[i, 0]), float(lvl[i, 1])) for i in range(count)]
 
     # ---- sharded single instance (include/shockwave_amd.h sw_dist_*) ----

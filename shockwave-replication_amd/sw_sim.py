@@ -4,8 +4,9 @@ Restates the part of the reference's ``Scheduler.simulate()``
 (scheduler/scheduler.py:1365-1796) that the Shockwave comparison runs:
 trace-driven arrivals, fixed-length rounds on a homogeneous v100 cluster,
 the Shockwave policy (plan solve on the GPU through ShockwaveScheduler) and
-the Gavel MaxMinFairness, water-filling MaxMinFairness and FinishTimeFairness
-(Themis) baselines (allocation program + deficit-based priorities),
+the Gavel MaxMinFairness, water-filling MaxMinFairness, FinishTimeFairness
+(Themis) and MinTotalDuration (makespan) baselines (allocation program +
+deficit-based priorities),
 dynamic batch-size scaling (GNS / Accordion) and the Fig-9 metrics.
 
 What is kept from the reference, and where it lives:
@@ -34,7 +35,9 @@ the product solvers (HIP, default) or with the CPU oracles (tests only):
     G) → x``, the same arguments;
   * FinishTimeFairness: ``ftf_allocator.ftf_allocate(scale_factors, full_time,
     elapsed, isolated_time, G) → (x, ρ*, μ)`` (the engine of the policy mirror
-    finish_time_fairness.py).
+    finish_time_fairness.py);
+  * MinTotalDuration: ``mtd_allocator.mtd_allocate(scale_factors, full_time,
+    G) → (x, T, μ)`` (the engine of the policy mirror min_total_duration.py).
 """
 from __future__ import annotations
 
@@ -58,15 +61,17 @@ WORKER_TYPE = "v100"  # the Shockwave hooks hard-code it (scheduler.py:1000, :36
 
 POLICY_NAMES = {"shockwave": "Shockwave", "max_min_fairness": "MaxMinFairness",
                 "finish_time_fairness": "FinishTimeFairness",
-                "max_min_fairness_water_filling": "MaxMinFairnessWaterFilling"}
+                "max_min_fairness_water_filling": "MaxMinFairnessWaterFilling",
+                "min_total_duration": "MinTotalDuration"}
 
 
 class Simulator:
     """One simulated cluster run (the reference's ``Scheduler`` with
     ``simulate=True``).
 
-    policy:           "shockwave", "max_min_fairness", "finish_time_fairness" or
-                      "max_min_fairness_water_filling" (utils.get_policy names)
+    policy:           "shockwave", "max_min_fairness", "finish_time_fairness",
+                      "max_min_fairness_water_filling" or "min_total_duration"
+                      (utils.get_policy names)
     throughputs:      {(job_type, scale_factor): v100 steps/s} (sw_trace.load_throughputs)
     profiles:         {int job id: profile dict} (the trace pickle; sw_trace.synthesize_profiles)
     shockwave_config: the JSON config + time_per_iteration + num_gpus (driver :60-70)
@@ -74,12 +79,13 @@ class Simulator:
     mmf_allocator:    MaxMinFairness allocation function (default: the HIP kernel)
     ftf_allocator:    FinishTimeFairness engine with ftf_allocate (default: the HIP solver)
     wf_allocator:     water-filling allocation function (default: the HIP kernel)
+    mtd_allocator:    MinTotalDuration engine with mtd_allocate (default: the HIP solver)
     """
 
     def __init__(self, policy, throughputs, profiles, time_per_iteration=120,
                  shockwave_config=None, shockwave_solver=None, mmf_allocator=None,
                  minimum_time_between_allocation_resets=1920, verbose=False, ftf_allocator=None,
-                 wf_allocator=None):
+                 wf_allocator=None, mtd_allocator=None):
         if policy not in POLICY_NAMES:
             raise ValueError(f"Unknown policy {policy!r} (supported: {sorted(POLICY_NAMES)})")
         self.policy_name = POLICY_NAMES[policy]
@@ -129,6 +135,8 @@ class Simulator:
         self._ftf_allocator = ftf_allocator
         self._ftf_policy = None
         self._wf_allocator = wf_allocator
+        self._mtd_allocator = mtd_allocator
+        self._mtd_policy = None
 
     # ---- helpers ------------------------------------------------------------------
     def _log(self, msg):
@@ -348,6 +356,8 @@ class Simulator:
         sf_j and c_j and returns x_j = min(1, L*/c_j)."""
         if self.policy_name == "FinishTimeFairness":
             return self._compute_ftf_allocation()
+        if self.policy_name == "MinTotalDuration":
+            return self._compute_mtd_allocation()
         ids = sorted(self._jobs.keys())
         if not ids:
             return {}
@@ -399,6 +409,34 @@ class Simulator:
         t0 = time.perf_counter()
         allocation = self._ftf_policy.get_allocation(throughputs, scale_factors, priority_weights,
                                                      times_since_start, num_steps_remaining, cluster_spec)
+        if allocation is None:
+            return {}
+        self.num_solves += 1
+        self.solve_seconds += time.perf_counter() - t0
+        return {j: float(allocation[j][WORKER_TYPE]) for j in allocation}
+
+    def _compute_mtd_allocation(self):
+        """scheduler.py:2351-2440 → policies/min_total_duration.py:11-106: the
+        allocation state of the FinishTimeFairness branch less the times."""
+        if self._mtd_policy is None:
+            try:
+                from . import sw_native
+                from .min_total_duration import MinTotalDurationPolicy
+            except ImportError:
+                import sw_native
+                from min_total_duration import MinTotalDurationPolicy
+            if self._mtd_allocator is None:
+                self._mtd_allocator = sw_native.Solver(device=0)
+            self._mtd_policy = MinTotalDurationPolicy(native=self._mtd_allocator)
+        jobs = self._jobs
+        throughputs = {j: {WORKER_TYPE: self._throughputs[j]} for j in jobs}
+        scale_factors = {j: jobs[j].scale_factor for j in jobs}
+        num_steps_remaining = {j: self._remaining_steps(j) for j in jobs}
+        cluster_spec = {WORKER_TYPE: len(self._worker_ids)}
+        import time
+        t0 = time.perf_counter()
+        allocation = self._mtd_policy.get_allocation(throughputs, scale_factors, num_steps_remaining,
+                                                     cluster_spec)
         if allocation is None:
             return {}
         self.num_solves += 1
@@ -631,7 +669,7 @@ class Simulator:
 
 def run_trace(policy, trace_file, num_gpus, time_per_iteration=120, config=None,
               throughputs=None, shockwave_solver=None, mmf_allocator=None, max_jobs=None,
-              verbose=False, ftf_allocator=None, wf_allocator=None):
+              verbose=False, ftf_allocator=None, wf_allocator=None, mtd_allocator=None):
     """The driver's main() (simulate_scheduler_with_trace.py:27-133): parse the
     trace, synthesise the profiles (the missing pickle), set job durations from
     them (:37-39), simulate, and return the Fig-9 metrics."""
@@ -650,6 +688,6 @@ def run_trace(policy, trace_file, num_gpus, time_per_iteration=120, config=None,
     sim = Simulator(policy, tp, profiles, time_per_iteration=time_per_iteration,
                     shockwave_config=sw_config, shockwave_solver=shockwave_solver,
                     mmf_allocator=mmf_allocator, verbose=verbose, ftf_allocator=ftf_allocator,
-                    wf_allocator=wf_allocator)
+                    wf_allocator=wf_allocator, mtd_allocator=mtd_allocator)
     sim.simulate(num_gpus, arrivals, jobs)
     return sim.summary()

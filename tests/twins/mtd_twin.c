@@ -1,0 +1,90 @@
+/*
+ * tests/twins/mtd_twin.c — TEST INFRASTRUCTURE: CPU bit-exact twin of the
+ * MinTotalDuration allocation kernel (shockwave-replication_amd/csrc/sw_mtd.hip).
+ *
+ * Same search (the state machine of sw_mtd.h), same per-job arithmetic
+ * (sw_mtd.h, sw_mmf.h, -ffp-contract=off) and the same deterministic job sums
+ * (sw_detsum: 512 contiguous chunks summed left to right, then the halving
+ * tree), so it returns the bits the GPU returns.  It is pinned against the
+ * reference's search by tests/test_mtd.py (tests/mtd_ref.py: the search over
+ * the closed-form predicate in exact rationals, and over the reference's LP
+ * through HiGHS).  Never linked into the product.
+ */
+#include <math.h>
+#include <stdint.h>
+
+#include "../../shockwave-replication_amd/csrc/sw_arith.h"
+#include "../../shockwave-replication_amd/csrc/sw_mmf.h"
+#include "../../shockwave-replication_amd/csrc/sw_mtd.h"
+
+static double detsum(const double* v, int32_t N) {
+    double part[SW_DET_LANES];
+    double wsum[SW_DET_LANES / 64];
+    int32_t q = (N + SW_DET_LANES - 1) / SW_DET_LANES;
+    for (int32_t lane = 0; lane < SW_DET_LANES; ++lane) {
+        double s = 0.0;
+        int32_t lo = lane * q, hi = lo + q < N ? lo + q : N;
+        for (int32_t j = lo; j < hi; ++j) s = s + v[j];
+        part[lane] = s;
+    }
+    for (int32_t w = 0; w < SW_DET_LANES / 64; ++w) {
+        double* p = part + 64 * w;
+        for (int32_t h = 32; h >= 1; h >>= 1)
+            for (int32_t i = 0; i < h; ++i) p[i] = p[i] + p[i + h];
+        wsum[w] = p[0];
+    }
+    for (int32_t h = SW_DET_LANES / 128; h >= 1; h >>= 1)
+        for (int32_t i = 0; i < h; ++i) wsum[i] = wsum[i] + wsum[i + h];
+    return wsum[0];
+}
+
+static double cap_at(int32_t N, const int32_t* sf, const double* p, double T, double* v) {
+    for (int32_t j = 0; j < N; ++j) v[j] = (double)sf[j] * sw_mtd_low(p[j], T);
+    return detsum(v, N);
+}
+
+/* v is caller scratch of N doubles; probes (optional) receives the number of
+ * T-probes the search took */
+int mtd_twin_allocate(int32_t N, int32_t G, const int32_t* sf, const double* p, double* x,
+                      double* level, double* v, int32_t* probes) {
+    if (level) { level[0] = 0.0; level[1] = 0.0; }
+    if (probes) *probes = 0;
+    if (N <= 0) return 0;
+    double maxp = 0.0;
+    for (int32_t j = 0; j < N; ++j) maxp = p[j] > maxp ? p[j] : maxp;
+    const double Gd = (double)G;
+
+    sw_mtd_search s;
+    sw_mtd_begin(&s);
+    double T = 0.0, cap = 0.0;
+    for (int it = 0; it < SW_MTD_MAX_PROBES && sw_mtd_next(&s, &T); ++it) {
+        int ok = 0;
+        if (maxp <= T) {
+            const double ct = cap_at(N, sf, p, T, v);
+            ok = ct <= Gd;
+            cap = ok ? ct : cap;
+        }
+        sw_mtd_feed(&s, T, ok);
+    }
+    T = sw_mtd_result(&s);
+    if (!s.have) cap = cap_at(N, sf, p, T, v);
+    if (probes) *probes = s.probes;
+
+    if (cap >= Gd) {
+        for (int32_t j = 0; j < N; ++j) x[j] = sw_mtd_low(p[j], T);
+        if (level) { level[0] = T; level[1] = 0.0; }
+        return 0;
+    }
+    uint64_t blo = SW_MMF_MU_LO, bhi = SW_MMF_MU_HI;
+    for (int it = 0; it < SW_MMF_ITERS && bhi - blo > 1; ++it) {
+        const uint64_t bmid = blo + (bhi - blo) / 2;
+        const double mu = sw_from_bits(bmid);
+        for (int32_t j = 0; j < N; ++j) v[j] = (double)sf[j] * sw_mtd_x((double)sf[j], p[j], T, mu);
+        const double slack = Gd - detsum(v, N);
+        if (slack > 0.0 && mu * slack >= 1.0) bhi = bmid; else blo = bmid;
+    }
+    const double mu = sw_from_bits(bhi);
+    for (int32_t j = 0; j < N; ++j) x[j] = sw_mtd_x((double)sf[j], p[j], T, mu);
+    if (level) { level[0] = T; level[1] = mu; }
+    return 0;
+}

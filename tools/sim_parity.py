@@ -47,7 +47,7 @@ def main():
     ap.add_argument("--solver", choices=["gpu", "twin", "milp"], default="gpu")
     ap.add_argument("--policies", default="shockwave,max_min_fairness",
                     help="comma-separated: shockwave, max_min_fairness, finish_time_fairness, "
-                         "max_min_fairness_water_filling")
+                         "max_min_fairness_water_filling, min_total_duration")
     ap.add_argument("--max-jobs", type=int, default=None)
     ap.add_argument("--time-per-iteration", type=int, default=120)
     ap.add_argument("--future-rounds", type=int, default=None,
@@ -65,6 +65,7 @@ def main():
         mmf = sn.MmfAllocator(solver=solver)
         ftf = solver
         wf = sn.WfAllocator(solver=solver)
+        mtd = solver
     else:
         import mmf_ref
         mmf = mmf_ref.twin_allocator
@@ -73,6 +74,8 @@ def main():
         ftf = ftf_ref.TwinEngine()
         import wf_ref
         wf = wf_ref.twin_allocator
+        import mtd_ref
+        mtd = mtd_ref.TwinEngine()
         if a.solver == "twin":
             solver = twin_solver()
         else:
@@ -86,7 +89,8 @@ def main():
         with contextlib.redirect_stdout(io.StringIO()):
             r = sw_sim.run_trace(pol, trace, a.gpus, a.time_per_iteration, cfg,
                                  shockwave_solver=solver, mmf_allocator=mmf,
-                                 max_jobs=a.max_jobs, ftf_allocator=ftf, wf_allocator=wf)
+                                 max_jobs=a.max_jobs, ftf_allocator=ftf, wf_allocator=wf,
+                                 mtd_allocator=mtd)
         r["wall_s"] = time.time() - t0
         out["runs"][pol] = r
         print(pol, json.dumps(r), flush=True)
