@@ -492,6 +492,51 @@ int sw_mtd_allocate_batch(sw_handle* h, int32_t count, const int64_t* offsets,
                           const int32_t* num_workers, const int32_t* scale_factors,
                           const double* full_time, double* allocation, double* levels);
 
+/*
+ * The Gavel max-sum-throughput baseline's allocation ("MST";
+ * policies/max_sum_throughput.py:39-96, selected as max_sum_throughput_perf in
+ * utils.get_policy) for one worker type.  The reference solves, with ECOS,
+ *     maximise Σ_j weight_j·x_j
+ *     s.t.     Σ_j scale_factor_j·x_j ≤ num_workers,  floor_j ≤ x_j ≤ 1,
+ * with weight_j = throughput_j / instance cost and floor_j = (steps_j / SLO_j)
+ * / throughput_j for a job with an SLO and steps_j / SLO_j > 0 (+inf when the
+ * throughput is 0), 0 otherwise; when the floors are infeasible (one above 1,
+ * or Σ_j scale_factor_j·floor_j > num_workers) it solves again without them.
+ * This call does both in one kernel: the density threshold λ of the
+ * fractional knapsack over weight_j / scale_factor_j (jobs above it get 1,
+ * jobs below it their floor) and, on the class of jobs tied at λ, the
+ * analytic centre of the optimal face (csrc/sw_mst.h; which point the
+ * reference's ECOS returns there is not pinned, ECOS is absent).  floors may
+ * be null: all zero.  allocation receives num_jobs doubles.  level (optional,
+ * 4 doubles) receives λ (0 when capacity is slack), the class multiplier (the
+ * signed ν of the capacity equality when λ > 0, the μ > 0 of the capacity
+ * barrier when λ = 0, 0 when the class is empty or its face is the single
+ * point at the floors), the objective Σ_j weight_j·x_j, and 1.0 when the
+ * floors were infeasible and dropped (0.0 otherwise).  SW_ERR_INVALID, with a
+ * message naming the rule: a scale factor outside [1, 255]; a weight that is
+ * not finite, < 0 or > 1e30; a floor that is NaN or < 0 (+inf is admitted);
+ * num_workers < 1; num_jobs < 0.  The handle keeps working after a rejected
+ * call.  Synchronous; num_jobs = 0 is a no-op with the level (0, 0, 0, 0)
+ * (policy.flatten returns None).
+ */
+int sw_mst_allocate(sw_handle* h, int32_t num_jobs, int32_t num_workers,
+                    const int32_t* scale_factors, const double* weights, const double* floors,
+                    double* allocation, double* level);
+
+/*
+ * count independent instances of sw_mst_allocate in one kernel launch (sweeps
+ * over cluster sizes and what-if states).  Instance i owns the jobs
+ * [offsets[i], offsets[i+1]) of the per-job arrays (CSR: count + 1 entries,
+ * offsets[0] = 0, never decreasing; an empty instance is allowed and yields
+ * the level (0, 0, 0, 0)) and num_workers[i] workers.  floors may be null.
+ * levels (optional) is [count][4].  Every instance's result is bit for bit
+ * that of the single call.  Synchronous; count = 0 is a no-op.
+ */
+int sw_mst_allocate_batch(sw_handle* h, int32_t count, const int64_t* offsets,
+                          const int32_t* num_workers, const int32_t* scale_factors,
+                          const double* weights, const double* floors, double* allocation,
+                          double* levels);
+
 #ifdef __cplusplus
 }
 #endif

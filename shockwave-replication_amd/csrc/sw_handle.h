@@ -133,6 +133,8 @@ struct sw_handle {
     void* wf = nullptr;
     /* MinTotalDuration allocation buffers (sw_mtd.hip) */
     void* mtd = nullptr;
+    /* max-sum-throughput allocation buffers (sw_mst.hip) */
+    void* mst = nullptr;
 };
 
 /* sw_shard.hip: frees the sharded-mode state and communicator */
@@ -145,4 +147,6 @@ void sw_ftf_release(sw_handle* h);
 void sw_wf_release(sw_handle* h);
 /* sw_mtd.hip: frees the MinTotalDuration buffers */
 void sw_mtd_release(sw_handle* h);
+/* sw_mst.hip: frees the max-sum-throughput buffers */
+void sw_mst_release(sw_handle* h);
 

@@ -319,6 +319,7 @@ EXPORTED_SYMBOLS = (
     "sw_dist_init_host", "sw_mmf_allocate", "sw_dist_plan_solve_dev", "sw_dist_enable_peer",
     "sw_mmf_allocate_types", "sw_batch_keep_masks", "sw_ftf_allocate", "sw_ftf_allocate_batch",
     "sw_wf_allocate", "sw_wf_allocate_batch", "sw_mtd_allocate", "sw_mtd_allocate_batch",
+    "sw_mst_allocate", "sw_mst_allocate_batch",
 )
 
 
@@ -407,6 +408,11 @@ def load(path: str | None = None):
     lib.sw_mtd_allocate.restype = C.c_int
     lib.sw_mtd_allocate_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _ip, _ip, _dp, _dp, _dp]
     lib.sw_mtd_allocate_batch.restype = C.c_int
+    lib.sw_mst_allocate.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip, _dp, _dp, _dp, _dp]
+    lib.sw_mst_allocate.restype = C.c_int
+    lib.sw_mst_allocate_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _ip, _ip, _dp, _dp, _dp,
+                                          _dp]
+    lib.sw_mst_allocate_batch.restype = C.c_int
     if path is None:
         _LIB = lib
     return lib
@@ -681,6 +687,58 @@ class Solver:
                                                    lvl.ctypes.data_as(_dp)),
                     "sw_mtd_allocate_batch")
         return [(x[off[i]:off[i + 1]].copy(), float(lvl[i, 0]), float(lvl[i, 1])) for i in range(count)]
+
+    # ---- Gavel max-sum-throughput allocation (include/shockwave_amd.h sw_mst_allocate) ----
+    @staticmethod
+    def _mst_arrays(scale_factors, weights, floors):
+        sf = np.ascontiguousarray(scale_factors, dtype=np.int32)
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        l = None if floors is None else np.ascontiguousarray(floors, dtype=np.float64)
+        if len(sf) != len(w) or (l is not None and len(l) != len(sf)):
+            raise ValueError("scale_factors, weights and floors must have the same length")
+        return sf, w, l
+
+    def mst_allocate(self, scale_factors, weights, floors, num_workers: int):
+        """x_j of the max-sum-throughput allocation (one worker type); floors
+        may be None (all zero).  Returns (x, λ, m, objective, slo_dropped)."""
+        sf, w, l = self._mst_arrays(scale_factors, weights, floors)
+        x = np.zeros(len(sf), dtype=np.float64)
+        lvl = np.zeros(4, dtype=np.float64)
+        self._check(self.lib.sw_mst_allocate(self.h, len(sf), int(num_workers), sf.ctypes.data_as(_ip),
+                                             w.ctypes.data_as(_dp), None if l is None else l.ctypes.data_as(_dp),
+                                             x.ctypes.data_as(_dp), lvl.ctypes.data_as(_dp)),
+                    "sw_mst_allocate")
+        return x, float(lvl[0]), float(lvl[1]), float(lvl[2]), bool(lvl[3])
+
+    def mst_allocate_batch(self, instances, offsets=None):
+        """sw_mst_allocate_batch over a list of (scale_factors, weights, floors,
+        num_workers) tuples, one kernel launch; returns the list of
+        (x, λ, m, objective, slo_dropped).  Floors of None are zeros (the
+        pointer is null when every instance has none).  offsets (tests only)
+        overrides the CSR offsets built from the instances' lengths."""
+        parts = [self._mst_arrays(*inst[:3]) for inst in instances]
+        count = len(parts)
+        off = np.zeros(count + 1, dtype=np.int64)
+        for i, q in enumerate(parts):
+            off[i + 1] = off[i] + len(q[0])
+        sf, w = [np.ascontiguousarray(np.concatenate([q[k] for q in parts]) if parts else [], dtype=t)
+                 for k, t in enumerate((np.int32, np.float64))]
+        l = None
+        if any(q[2] is not None for q in parts):
+            l = np.ascontiguousarray(np.concatenate([np.zeros(len(q[0])) if q[2] is None else q[2] for q in parts]),
+                                     dtype=np.float64)
+        g = np.ascontiguousarray([int(inst[3]) for inst in instances], dtype=np.int32)
+        x = np.zeros(len(sf), dtype=np.float64)
+        lvl = np.zeros((count, 4), dtype=np.float64)
+        coff = off if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
+        self._check(self.lib.sw_mst_allocate_batch(self.h, count, coff.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                   g.ctypes.data_as(_ip), sf.ctypes.data_as(_ip),
+                                                   w.ctypes.data_as(_dp),
+                                                   None if l is None else l.ctypes.data_as(_dp),
+                                                   x.ctypes.data_as(_dp), lvl.ctypes.data_as(_dp)),
+                    "sw_mst_allocate_batch")
+        return [(x[off[i]:off[i + 1]].copy(), float(lvl[i, 0]), float(lvl[i, 1]), float(lvl[i, 2]), bool(lvl[i, 3]))
+                for i in range(count)]
 
     # ---- sharded single instance (include/shockwave_amd.h sw_dist_*) ----
     def dist_init(self, unique_id: bytes, rank: int, world: int):

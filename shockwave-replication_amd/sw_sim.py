@@ -5,8 +5,8 @@ Restates the part of the reference's ``Scheduler.simulate()``
 trace-driven arrivals, fixed-length rounds on a homogeneous v100 cluster,
 the Shockwave policy (plan solve on the GPU through ShockwaveScheduler) and
 the Gavel MaxMinFairness, water-filling MaxMinFairness, FinishTimeFairness
-(Themis) and MinTotalDuration (makespan) baselines (allocation program +
-deficit-based priorities),
+(Themis), MinTotalDuration (makespan) and max-sum-throughput baselines
+(allocation program + deficit-based priorities),
 dynamic batch-size scaling (GNS / Accordion) and the Fig-9 metrics.
 
 What is kept from the reference, and where it lives:
@@ -37,7 +37,10 @@ the product solvers (HIP, default) or with the CPU oracles (tests only):
     elapsed, isolated_time, G) → (x, ρ*, μ)`` (the engine of the policy mirror
     finish_time_fairness.py);
   * MinTotalDuration: ``mtd_allocator.mtd_allocate(scale_factors, full_time,
-    G) → (x, T, μ)`` (the engine of the policy mirror min_total_duration.py).
+    G) → (x, T, μ)`` (the engine of the policy mirror min_total_duration.py);
+  * ThroughputSumWithPerf: ``mst_allocator.mst_allocate(scale_factors, weights,
+    floors, G) → (x, λ, m, objective, slo_dropped)`` (the engine of the policy
+    mirror max_sum_throughput.py; the simulator passes no SLOs and no costs).
 """
 from __future__ import annotations
 
@@ -62,7 +65,8 @@ WORKER_TYPE = "v100"  # the Shockwave hooks hard-code it (scheduler.py:1000, :36
 POLICY_NAMES = {"shockwave": "Shockwave", "max_min_fairness": "MaxMinFairness",
                 "finish_time_fairness": "FinishTimeFairness",
                 "max_min_fairness_water_filling": "MaxMinFairnessWaterFilling",
-                "min_total_duration": "MinTotalDuration"}
+                "min_total_duration": "MinTotalDuration",
+                "max_sum_throughput_perf": "ThroughputSumWithPerf"}
 
 
 class Simulator:
@@ -70,8 +74,8 @@ class Simulator:
     ``simulate=True``).
 
     policy:           "shockwave", "max_min_fairness", "finish_time_fairness",
-                      "max_min_fairness_water_filling" or "min_total_duration"
-                      (utils.get_policy names)
+                      "max_min_fairness_water_filling", "min_total_duration" or
+                      "max_sum_throughput_perf" (utils.get_policy names)
     throughputs:      {(job_type, scale_factor): v100 steps/s} (sw_trace.load_throughputs)
     profiles:         {int job id: profile dict} (the trace pickle; sw_trace.synthesize_profiles)
     shockwave_config: the JSON config + time_per_iteration + num_gpus (driver :60-70)
@@ -80,12 +84,13 @@ class Simulator:
     ftf_allocator:    FinishTimeFairness engine with ftf_allocate (default: the HIP solver)
     wf_allocator:     water-filling allocation function (default: the HIP kernel)
     mtd_allocator:    MinTotalDuration engine with mtd_allocate (default: the HIP solver)
+    mst_allocator:    max-sum-throughput engine with mst_allocate (default: the HIP solver)
     """
 
     def __init__(self, policy, throughputs, profiles, time_per_iteration=120,
                  shockwave_config=None, shockwave_solver=None, mmf_allocator=None,
                  minimum_time_between_allocation_resets=1920, verbose=False, ftf_allocator=None,
-                 wf_allocator=None, mtd_allocator=None):
+                 wf_allocator=None, mtd_allocator=None, mst_allocator=None):
         if policy not in POLICY_NAMES:
             raise ValueError(f"Unknown policy {policy!r} (supported: {sorted(POLICY_NAMES)})")
         self.policy_name = POLICY_NAMES[policy]
@@ -137,6 +142,8 @@ class Simulator:
         self._wf_allocator = wf_allocator
         self._mtd_allocator = mtd_allocator
         self._mtd_policy = None
+        self._mst_allocator = mst_allocator
+        self._mst_policy = None
 
     # ---- helpers ------------------------------------------------------------------
     def _log(self, msg):
@@ -358,6 +365,8 @@ class Simulator:
             return self._compute_ftf_allocation()
         if self.policy_name == "MinTotalDuration":
             return self._compute_mtd_allocation()
+        if self.policy_name == "ThroughputSumWithPerf":
+            return self._compute_mst_allocation()
         ids = sorted(self._jobs.keys())
         if not ids:
             return {}
@@ -437,6 +446,34 @@ class Simulator:
         t0 = time.perf_counter()
         allocation = self._mtd_policy.get_allocation(throughputs, scale_factors, num_steps_remaining,
                                                      cluster_spec)
+        if allocation is None:
+            return {}
+        self.num_solves += 1
+        self.solve_seconds += time.perf_counter() - t0
+        return {j: float(allocation[j][WORKER_TYPE]) for j in allocation}
+
+    def _compute_mst_allocation(self):
+        """scheduler.py:2351-2411, :2460-2463 → policies/max_sum_throughput.py:11-96:
+        throughputs, scale factors and the cluster, no SLOs and no instance
+        costs.  A job the optimum starves gets 0.0, which _update_priorities
+        turns into priority 0."""
+        if self._mst_policy is None:
+            try:
+                from . import sw_native
+                from .max_sum_throughput import ThroughputSumWithPerf
+            except ImportError:
+                import sw_native
+                from max_sum_throughput import ThroughputSumWithPerf
+            if self._mst_allocator is None:
+                self._mst_allocator = sw_native.Solver(device=0)
+            self._mst_policy = ThroughputSumWithPerf(native=self._mst_allocator)
+        jobs = self._jobs
+        throughputs = {j: {WORKER_TYPE: self._throughputs[j]} for j in jobs}
+        scale_factors = {j: jobs[j].scale_factor for j in jobs}
+        cluster_spec = {WORKER_TYPE: len(self._worker_ids)}
+        import time
+        t0 = time.perf_counter()
+        allocation = self._mst_policy.get_allocation(throughputs, scale_factors, cluster_spec)
         if allocation is None:
             return {}
         self.num_solves += 1
@@ -669,7 +706,8 @@ class Simulator:
 
 def run_trace(policy, trace_file, num_gpus, time_per_iteration=120, config=None,
               throughputs=None, shockwave_solver=None, mmf_allocator=None, max_jobs=None,
-              verbose=False, ftf_allocator=None, wf_allocator=None, mtd_allocator=None):
+              verbose=False, ftf_allocator=None, wf_allocator=None, mtd_allocator=None,
+              mst_allocator=None):
     """The driver's main() (simulate_scheduler_with_trace.py:27-133): parse the
     trace, synthesise the profiles (the missing pickle), set job durations from
     them (:37-39), simulate, and return the Fig-9 metrics."""
@@ -688,6 +726,7 @@ def run_trace(policy, trace_file, num_gpus, time_per_iteration=120, config=None,
     sim = Simulator(policy, tp, profiles, time_per_iteration=time_per_iteration,
                     shockwave_config=sw_config, shockwave_solver=shockwave_solver,
                     mmf_allocator=mmf_allocator, verbose=verbose, ftf_allocator=ftf_allocator,
-                    wf_allocator=wf_allocator, mtd_allocator=mtd_allocator)
+                    wf_allocator=wf_allocator, mtd_allocator=mtd_allocator,
+                    mst_allocator=mst_allocator)
     sim.simulate(num_gpus, arrivals, jobs)
     return sim.summary()

@@ -47,7 +47,7 @@ def main():
     ap.add_argument("--solver", choices=["gpu", "twin", "milp"], default="gpu")
     ap.add_argument("--policies", default="shockwave,max_min_fairness",
                     help="comma-separated: shockwave, max_min_fairness, finish_time_fairness, "
-                         "max_min_fairness_water_filling, min_total_duration")
+                         "max_min_fairness_water_filling, min_total_duration, max_sum_throughput_perf")
     ap.add_argument("--max-jobs", type=int, default=None)
     ap.add_argument("--time-per-iteration", type=int, default=120)
     ap.add_argument("--future-rounds", type=int, default=None,
@@ -66,6 +66,7 @@ def main():
         ftf = solver
         wf = sn.WfAllocator(solver=solver)
         mtd = solver
+        mst = solver
     else:
         import mmf_ref
         mmf = mmf_ref.twin_allocator
@@ -76,6 +77,8 @@ def main():
         wf = wf_ref.twin_allocator
         import mtd_ref
         mtd = mtd_ref.TwinEngine()
+        import mst_ref
+        mst = mst_ref.TwinEngine()
         if a.solver == "twin":
             solver = twin_solver()
         else:
@@ -90,7 +93,7 @@ def main():
             r = sw_sim.run_trace(pol, trace, a.gpus, a.time_per_iteration, cfg,
                                  shockwave_solver=solver, mmf_allocator=mmf,
                                  max_jobs=a.max_jobs, ftf_allocator=ftf, wf_allocator=wf,
-                                 mtd_allocator=mtd)
+                                 mtd_allocator=mtd, mst_allocator=mst)
         r["wall_s"] = time.time() - t0
         out["runs"][pol] = r
         print(pol, json.dumps(r), flush=True)
