@@ -537,6 +537,67 @@ int sw_mst_allocate_batch(sw_handle* h, int32_t count, const int64_t* offsets,
                           const double* weights, const double* floors, double* allocation,
                           double* levels);
 
+/*
+ * The AlloX baseline's assignment (policies/allox.py:71-118, selected as
+ * allox / allox_alpha=<a> in utils.get_policy).  The reference places the
+ * num_jobs jobs that hold no worker on the free workers by a min-cost
+ * bipartite assignment (scipy.optimize.linear_sum_assignment, :103) over a
+ * dense num_jobs × (num_jobs·n) matrix, n = Σ free_workers: job i in column
+ * (free worker j, position k), k = 1..num_jobs, costs
+ *     k·proc_time[i][type(j)] + delay[i]                       (:83-100)
+ * with proc_time = steps remaining / throughput (:77-82) and delay = time
+ * since start (:93).  Position 1 runs last; on every worker the job at the
+ * highest used position runs first and is the one the policy allocates
+ * (:113-134).  This call finds an assignment of the same, minimal, total cost
+ * in one kernel without building the matrix (csrc/sw_allox.h: shortest
+ * augmenting paths over at most num_jobs + n live columns).  The optimal
+ * cost is unique, the assignment is not (workers of one type are identical
+ * columns); ties are decided by the rule stated in csrc/sw_allox.h — smallest
+ * distance, then an unassigned column before an assigned one, then the lowest
+ * worker index — not by scipy's.
+ *   free_workers   [num_types], each ≥ 0.  Free workers are numbered
+ *                  type-major: the first free_workers[0] are type 0 (:57-64).
+ *   proc_time      [num_jobs][num_types], row-major
+ *   delay          [num_jobs]
+ *   job_worker     [num_jobs]: the job's free-worker index
+ *   job_position   [num_jobs]: k ≥ 1, 1 = runs last; positions on a worker are
+ *                  1..len without gaps
+ *   worker_first   [n]: the job that runs first on the worker, −1 = idle
+ *   cost           optional: Σ_i job_position[i]·proc_time[i][type] + delay[i],
+ *                  summed in job order
+ * SW_ALLOX_MAX_TYPES = 8.  num_jobs ≤ 1024 and n ≤ 1024; more is
+ * SW_ERR_CAPACITY.  SW_ERR_INVALID, with a message naming the rule: a
+ * proc_time that is not finite, < 0 or > 1e30; a delay that is not finite,
+ * < 0 or > 1e15; a negative worker count; num_types outside [1, 8];
+ * num_jobs < 0.  The handle keeps working after a rejected call.
+ * Synchronous; num_jobs = 0 or n = 0 is a no-op that returns SW_OK with every
+ * job unassigned (−1, 0), every worker idle and cost 0 (:49, :131: nothing is
+ * assigned and the previous rows are copied).
+ */
+#define SW_ALLOX_MAX_TYPES 8
+int sw_allox_assign(sw_handle* h, int32_t num_jobs, int32_t num_types,
+                    const int32_t* free_workers, const double* proc_time, const double* delay,
+                    int32_t* job_worker, int32_t* job_position, int32_t* worker_first,
+                    double* cost);
+
+/*
+ * count independent instances of sw_allox_assign in one kernel launch.
+ * Instance i owns the jobs [job_offsets[i], job_offsets[i+1]) of delay,
+ * job_worker and job_position, the free workers [worker_offsets[i],
+ * worker_offsets[i+1]) of worker_first (both CSR: count + 1 entries, first 0,
+ * never decreasing; worker_offsets must step by Σ free_workers[i]),
+ * num_types[i] types with the counts free_workers[i][0..num_types[i]) of the
+ * [count][SW_ALLOX_MAX_TYPES] array, and the next num_jobs_i·num_types[i]
+ * entries of proc_time (instances concatenated).  costs (optional) is
+ * [count].  Every instance's result is bit for bit that of the single call.
+ * Synchronous; count = 0 is a no-op.
+ */
+int sw_allox_assign_batch(sw_handle* h, int32_t count, const int64_t* job_offsets,
+                          const int32_t* num_types, const int32_t* free_workers,
+                          const double* proc_time, const double* delay, int32_t* job_worker,
+                          int32_t* job_position, int32_t* worker_first,
+                          const int64_t* worker_offsets, double* costs);
+
 #ifdef __cplusplus
 }
 #endif

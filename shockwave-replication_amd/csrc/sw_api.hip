@@ -230,6 +230,7 @@ void sw_destroy(sw_handle* h) {
     sw_wf_release(h);
     sw_mtd_release(h);
     sw_mst_release(h);
+    sw_allox_release(h);
     h->d_in.release(); h->d_res.release();
     h->d_ws_u8.release(); h->d_ws_u64.release(); h->d_ws_sort.release();
     h->d_ws_keys.release(); h->d_ws_jc.release(); h->d_stamps.release();

@@ -135,6 +135,8 @@ struct sw_handle {
     void* mtd = nullptr;
     /* max-sum-throughput allocation buffers (sw_mst.hip) */
     void* mst = nullptr;
+    /* AlloX assignment buffers (sw_allox.hip) */
+    void* allox = nullptr;
 };
 
 /* sw_shard.hip: frees the sharded-mode state and communicator */
@@ -149,4 +151,6 @@ void sw_wf_release(sw_handle* h);
 void sw_mtd_release(sw_handle* h);
 /* sw_mst.hip: frees the max-sum-throughput buffers */
 void sw_mst_release(sw_handle* h);
+/* sw_allox.hip: frees the AlloX buffers */
+void sw_allox_release(sw_handle* h);
 

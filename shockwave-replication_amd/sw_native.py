@@ -319,7 +319,7 @@ EXPORTED_SYMBOLS = (
     "sw_dist_init_host", "sw_mmf_allocate", "sw_dist_plan_solve_dev", "sw_dist_enable_peer",
     "sw_mmf_allocate_types", "sw_batch_keep_masks", "sw_ftf_allocate", "sw_ftf_allocate_batch",
     "sw_wf_allocate", "sw_wf_allocate_batch", "sw_mtd_allocate", "sw_mtd_allocate_batch",
-    "sw_mst_allocate", "sw_mst_allocate_batch",
+    "sw_mst_allocate", "sw_mst_allocate_batch", "sw_allox_assign", "sw_allox_assign_batch",
 )
 
 
@@ -413,6 +413,11 @@ def load(path: str | None = None):
     lib.sw_mst_allocate_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _ip, _ip, _dp, _dp, _dp,
                                           _dp]
     lib.sw_mst_allocate_batch.restype = C.c_int
+    lib.sw_allox_assign.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip, _dp, _dp, _ip, _ip, _ip, _dp]
+    lib.sw_allox_assign.restype = C.c_int
+    lib.sw_allox_assign_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _ip, _ip, _dp, _dp, _ip, _ip,
+                                          _ip, C.POINTER(C.c_int64), _dp]
+    lib.sw_allox_assign_batch.restype = C.c_int
     if path is None:
         _LIB = lib
     return lib
@@ -739,6 +744,65 @@ class Solver:
                     "sw_mst_allocate_batch")
         return [(x[off[i]:off[i + 1]].copy(), float(lvl[i, 0]), float(lvl[i, 1]), float(lvl[i, 2]), bool(lvl[i, 3]))
                 for i in range(count)]
+
+    # ---- AlloX assignment (include/shockwave_amd.h sw_allox_assign) ----
+    @staticmethod
+    def _allox_arrays(free_workers, proc_time, delay):
+        free = np.ascontiguousarray(free_workers, dtype=np.int32).reshape(-1)
+        d = np.ascontiguousarray(delay, dtype=np.float64).reshape(-1)
+        p = np.ascontiguousarray(proc_time, dtype=np.float64)
+        if p.size != len(d) * len(free):
+            raise ValueError("proc_time must be [len(delay)][len(free_workers)]")
+        return free, p.reshape(len(d), len(free)), d
+
+    def allox_assign(self, free_workers, proc_time, delay):
+        """The AlloX min-cost assignment of len(delay) jobs to the free workers
+        (per type, type-major).  Returns (job_worker, job_position,
+        worker_first, cost)."""
+        free, p, d = self._allox_arrays(free_workers, proc_time, delay)
+        m, n = len(d), int(np.clip(free, 0, None).sum())
+        jw = np.full(m, -1, dtype=np.int32)
+        jp = np.zeros(m, dtype=np.int32)
+        wf = np.full(max(n, 1), -1, dtype=np.int32)
+        cost = C.c_double(0.0)
+        self._check(self.lib.sw_allox_assign(self.h, m, len(free), free.ctypes.data_as(_ip), p.ctypes.data_as(_dp),
+                                             d.ctypes.data_as(_dp), jw.ctypes.data_as(_ip), jp.ctypes.data_as(_ip),
+                                             wf.ctypes.data_as(_ip), C.byref(cost)),
+                    "sw_allox_assign")
+        return jw, jp, wf[:n].copy(), float(cost.value)
+
+    def allox_assign_batch(self, instances):
+        """sw_allox_assign_batch over a list of (free_workers, proc_time, delay)
+        tuples, one kernel launch; returns the list of (job_worker,
+        job_position, worker_first, cost)."""
+        parts = [self._allox_arrays(*inst) for inst in instances]
+        count = len(parts)
+        joff = np.zeros(count + 1, dtype=np.int64)
+        woff = np.zeros(count + 1, dtype=np.int64)
+        free = np.zeros((count, 8), dtype=np.int32)
+        nt = np.zeros(count, dtype=np.int32)
+        for i, (f, p, d) in enumerate(parts):
+            if len(f) > 8:
+                raise ValueError("at most 8 worker types")
+            joff[i + 1] = joff[i] + len(d)
+            woff[i + 1] = woff[i] + int(np.clip(f, 0, None).sum())
+            free[i, :len(f)] = f
+            nt[i] = len(f)
+        p = np.ascontiguousarray(np.concatenate([q[1].reshape(-1) for q in parts]) if parts else [], dtype=np.float64)
+        d = np.ascontiguousarray(np.concatenate([q[2] for q in parts]) if parts else [], dtype=np.float64)
+        jw = np.full(len(d), -1, dtype=np.int32)
+        jp = np.zeros(len(d), dtype=np.int32)
+        wf = np.full(max(int(woff[-1]), 1), -1, dtype=np.int32)
+        costs = np.zeros(max(count, 1), dtype=np.float64)
+        lp = C.POINTER(C.c_int64)
+        self._check(self.lib.sw_allox_assign_batch(self.h, count, joff.ctypes.data_as(lp), nt.ctypes.data_as(_ip),
+                                                   free.ctypes.data_as(_ip), p.ctypes.data_as(_dp),
+                                                   d.ctypes.data_as(_dp), jw.ctypes.data_as(_ip),
+                                                   jp.ctypes.data_as(_ip), wf.ctypes.data_as(_ip),
+                                                   woff.ctypes.data_as(lp), costs.ctypes.data_as(_dp)),
+                    "sw_allox_assign_batch")
+        return [(jw[joff[i]:joff[i + 1]].copy(), jp[joff[i]:joff[i + 1]].copy(), wf[woff[i]:woff[i + 1]].copy(),
+                 float(costs[i])) for i in range(count)]
 
     # ---- sharded single instance (include/shockwave_amd.h sw_dist_*) ----
     def dist_init(self, unique_id: bytes, rank: int, world: int):

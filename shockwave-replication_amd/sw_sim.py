@@ -5,8 +5,8 @@ Restates the part of the reference's ``Scheduler.simulate()``
 trace-driven arrivals, fixed-length rounds on a homogeneous v100 cluster,
 the Shockwave policy (plan solve on the GPU through ShockwaveScheduler) and
 the Gavel MaxMinFairness, water-filling MaxMinFairness, FinishTimeFairness
-(Themis), MinTotalDuration (makespan) and max-sum-throughput baselines
-(allocation program + deficit-based priorities),
+(Themis), MinTotalDuration (makespan), max-sum-throughput and AlloX baselines
+(allocation program or assignment + deficit-based priorities),
 dynamic batch-size scaling (GNS / Accordion) and the Fig-9 metrics.
 
 What is kept from the reference, and where it lives:
@@ -40,7 +40,12 @@ the product solvers (HIP, default) or with the CPU oracles (tests only):
     G) → (x, T, μ)`` (the engine of the policy mirror min_total_duration.py);
   * ThroughputSumWithPerf: ``mst_allocator.mst_allocate(scale_factors, weights,
     floors, G) → (x, λ, m, objective, slo_dropped)`` (the engine of the policy
-    mirror max_sum_throughput.py; the simulator passes no SLOs and no costs).
+    mirror max_sum_throughput.py; the simulator passes no SLOs and no costs);
+  * AlloX: ``allox_allocator.allox_assign(free_workers, proc_time, delay) →
+    (job_worker, job_position, worker_first, cost)`` (the engine of the policy
+    mirror allox.py).  AlloX places single-GPU jobs only: a trace job whose
+    scale factor is not 1 raises the reference's ``AssertionError``
+    (allox.py:35-36) at the first allocation that sees it.
 """
 from __future__ import annotations
 
@@ -66,7 +71,19 @@ POLICY_NAMES = {"shockwave": "Shockwave", "max_min_fairness": "MaxMinFairness",
                 "finish_time_fairness": "FinishTimeFairness",
                 "max_min_fairness_water_filling": "MaxMinFairnessWaterFilling",
                 "min_total_duration": "MinTotalDuration",
-                "max_sum_throughput_perf": "ThroughputSumWithPerf"}
+                "max_sum_throughput_perf": "ThroughputSumWithPerf",
+                "allox": "AlloX_Perf"}
+ALLOX_ALPHA_PREFIX = "allox_alpha="  # utils.get_policy :485-490
+
+
+def _allox_alpha(policy):
+    """The alpha of "allox" / "allox_alpha=<a>" (utils.py:485-490), None for
+    every other policy name."""
+    if policy == "allox":
+        return 1.0
+    if isinstance(policy, str) and policy.startswith(ALLOX_ALPHA_PREFIX):
+        return float(policy[len(ALLOX_ALPHA_PREFIX):])
+    return None
 
 
 class Simulator:
@@ -74,8 +91,9 @@ class Simulator:
     ``simulate=True``).
 
     policy:           "shockwave", "max_min_fairness", "finish_time_fairness",
-                      "max_min_fairness_water_filling", "min_total_duration" or
-                      "max_sum_throughput_perf" (utils.get_policy names)
+                      "max_min_fairness_water_filling", "min_total_duration",
+                      "max_sum_throughput_perf", "allox" or "allox_alpha=<a>"
+                      (utils.get_policy names)
     throughputs:      {(job_type, scale_factor): v100 steps/s} (sw_trace.load_throughputs)
     profiles:         {int job id: profile dict} (the trace pickle; sw_trace.synthesize_profiles)
     shockwave_config: the JSON config + time_per_iteration + num_gpus (driver :60-70)
@@ -85,12 +103,18 @@ class Simulator:
     wf_allocator:     water-filling allocation function (default: the HIP kernel)
     mtd_allocator:    MinTotalDuration engine with mtd_allocate (default: the HIP solver)
     mst_allocator:    max-sum-throughput engine with mst_allocate (default: the HIP solver)
+    allox_allocator:  AlloX engine with allox_assign (default: the HIP solver).  AlloX
+                      takes single-GPU jobs only: a job with scale factor != 1 raises
+                      the reference's AssertionError (allox.py:35-36)
     """
 
     def __init__(self, policy, throughputs, profiles, time_per_iteration=120,
                  shockwave_config=None, shockwave_solver=None, mmf_allocator=None,
                  minimum_time_between_allocation_resets=1920, verbose=False, ftf_allocator=None,
-                 wf_allocator=None, mtd_allocator=None, mst_allocator=None):
+                 wf_allocator=None, mtd_allocator=None, mst_allocator=None, allox_allocator=None):
+        self._allox_alpha = _allox_alpha(policy)
+        if self._allox_alpha is not None:
+            policy = "allox"
         if policy not in POLICY_NAMES:
             raise ValueError(f"Unknown policy {policy!r} (supported: {sorted(POLICY_NAMES)})")
         self.policy_name = POLICY_NAMES[policy]
@@ -144,6 +168,8 @@ class Simulator:
         self._mtd_policy = None
         self._mst_allocator = mst_allocator
         self._mst_policy = None
+        self._allox_allocator = allox_allocator
+        self._allox_policy = None
 
     # ---- helpers ------------------------------------------------------------------
     def _log(self, msg):
@@ -367,6 +393,8 @@ class Simulator:
             return self._compute_mtd_allocation()
         if self.policy_name == "ThroughputSumWithPerf":
             return self._compute_mst_allocation()
+        if self.policy_name == "AlloX_Perf":
+            return self._compute_allox_allocation()
         ids = sorted(self._jobs.keys())
         if not ids:
             return {}
@@ -474,6 +502,37 @@ class Simulator:
         import time
         t0 = time.perf_counter()
         allocation = self._mst_policy.get_allocation(throughputs, scale_factors, cluster_spec)
+        if allocation is None:
+            return {}
+        self.num_solves += 1
+        self.solve_seconds += time.perf_counter() - t0
+        return {j: float(allocation[j][WORKER_TYPE]) for j in allocation}
+
+    def _compute_allox_allocation(self):
+        """scheduler.py:2351-2419 → policies/allox.py:13-141: the allocation
+        state of the FinishTimeFairness branch less the priority weights.  The
+        mirror keeps the previous allocation between calls (a job that holds a
+        worker keeps it) and asserts that every scale factor is 1."""
+        if self._allox_policy is None:
+            try:
+                from . import sw_native
+                from .allox import AlloXPolicy
+            except ImportError:
+                import sw_native
+                from allox import AlloXPolicy
+            if self._allox_allocator is None:
+                self._allox_allocator = sw_native.Solver(device=0)
+            self._allox_policy = AlloXPolicy(alpha=self._allox_alpha, native=self._allox_allocator)
+        jobs = self._jobs
+        throughputs = {j: {WORKER_TYPE: self._throughputs[j]} for j in jobs}
+        scale_factors = {j: jobs[j].scale_factor for j in jobs}
+        num_steps_remaining = {j: self._remaining_steps(j) for j in jobs}
+        times_since_start = {j: self._current_timestamp - self._per_job_start_timestamps[j] for j in jobs}
+        cluster_spec = {WORKER_TYPE: len(self._worker_ids)}
+        import time
+        t0 = time.perf_counter()
+        allocation = self._allox_policy.get_allocation(throughputs, scale_factors, times_since_start,
+                                                       num_steps_remaining, cluster_spec)
         if allocation is None:
             return {}
         self.num_solves += 1
@@ -707,12 +766,17 @@ class Simulator:
 def run_trace(policy, trace_file, num_gpus, time_per_iteration=120, config=None,
               throughputs=None, shockwave_solver=None, mmf_allocator=None, max_jobs=None,
               verbose=False, ftf_allocator=None, wf_allocator=None, mtd_allocator=None,
-              mst_allocator=None):
+              mst_allocator=None, allox_allocator=None, single_gpu_jobs=False):
     """The driver's main() (simulate_scheduler_with_trace.py:27-133): parse the
     trace, synthesise the profiles (the missing pickle), set job durations from
-    them (:37-39), simulate, and return the Fig-9 metrics."""
+    them (:37-39), simulate, and return the Fig-9 metrics.  single_gpu_jobs
+    keeps only the trace's jobs of scale factor 1 (before max_jobs cuts): what
+    AlloX can place."""
     tp = throughputs if throughputs is not None else st.load_throughputs()
     jobs, arrivals = st.parse_trace(trace_file)
+    if single_gpu_jobs:
+        keep = [i for i, j in enumerate(jobs) if j.scale_factor == 1]
+        jobs, arrivals = [jobs[i] for i in keep], [arrivals[i] for i in keep]
     if max_jobs is not None:
         jobs, arrivals = jobs[:max_jobs], arrivals[:max_jobs]
     profiles = st.synthesize_profiles(jobs, tp)
@@ -727,6 +791,6 @@ def run_trace(policy, trace_file, num_gpus, time_per_iteration=120, config=None,
                     shockwave_config=sw_config, shockwave_solver=shockwave_solver,
                     mmf_allocator=mmf_allocator, verbose=verbose, ftf_allocator=ftf_allocator,
                     wf_allocator=wf_allocator, mtd_allocator=mtd_allocator,
-                    mst_allocator=mst_allocator)
+                    mst_allocator=mst_allocator, allox_allocator=allox_allocator)
     sim.simulate(num_gpus, arrivals, jobs)
     return sim.summary()

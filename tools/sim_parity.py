@@ -47,7 +47,10 @@ def main():
     ap.add_argument("--solver", choices=["gpu", "twin", "milp"], default="gpu")
     ap.add_argument("--policies", default="shockwave,max_min_fairness",
                     help="comma-separated: shockwave, max_min_fairness, finish_time_fairness, "
-                         "max_min_fairness_water_filling, min_total_duration, max_sum_throughput_perf")
+                         "max_min_fairness_water_filling, min_total_duration, max_sum_throughput_perf, "
+                         "allox, allox_alpha=<a> (these two need --single-gpu-jobs on the shipped traces)")
+    ap.add_argument("--single-gpu-jobs", action="store_true",
+                    help="keep only the trace's jobs of scale factor 1 (AlloX places no others)")
     ap.add_argument("--max-jobs", type=int, default=None)
     ap.add_argument("--time-per-iteration", type=int, default=120)
     ap.add_argument("--future-rounds", type=int, default=None,
@@ -67,6 +70,7 @@ def main():
         wf = sn.WfAllocator(solver=solver)
         mtd = solver
         mst = solver
+        allox = solver
     else:
         import mmf_ref
         mmf = mmf_ref.twin_allocator
@@ -79,6 +83,8 @@ def main():
         mtd = mtd_ref.TwinEngine()
         import mst_ref
         mst = mst_ref.TwinEngine()
+        import allox_ref
+        allox = allox_ref.TwinEngine()
         if a.solver == "twin":
             solver = twin_solver()
         else:
@@ -86,14 +92,15 @@ def main():
             solver = milp_ref.MilpSolver()
     out = {"trace": a.trace, "gpus": a.gpus, "solver": a.solver, "config": cfg_name,
            "future_rounds": cfg["future_rounds"],
-           "time_per_iteration": a.time_per_iteration, "runs": {}}
+           "time_per_iteration": a.time_per_iteration, "single_gpu_jobs": a.single_gpu_jobs, "runs": {}}
     for pol in a.policies.split(","):
         t0 = time.time()
         with contextlib.redirect_stdout(io.StringIO()):
             r = sw_sim.run_trace(pol, trace, a.gpus, a.time_per_iteration, cfg,
                                  shockwave_solver=solver, mmf_allocator=mmf,
                                  max_jobs=a.max_jobs, ftf_allocator=ftf, wf_allocator=wf,
-                                 mtd_allocator=mtd, mst_allocator=mst)
+                                 mtd_allocator=mtd, mst_allocator=mst, allox_allocator=allox,
+                                 single_gpu_jobs=a.single_gpu_jobs)
         r["wall_s"] = time.time() - t0
         out["runs"][pol] = r
         print(pol, json.dumps(r), flush=True)
