@@ -212,32 +212,15 @@ __global__ __launch_bounds__(64 * NW) void sw_allox_kernel(
  *        | free [count][8] | num_types [count] (int32)
  *   out: costs [count] (double) | job_worker [M] | job_position [M] | worker_first [W]
  *        | status [count] (int32) */
-struct AlloxBufs {
-    DevBuf<unsigned char> in, out;
-    HostBuf<unsigned char> hin, hout;
-};
-
-int allox_fail(sw_handle* h, int code, const std::string& msg) {
-    h->err = msg;
-    return code;
-}
-
-#define ALLOX_HIP(h, call)                                                                      \
-    do {                                                                                        \
-        hipError_t _e = (call);                                                                 \
-        if (_e != hipSuccess)                                                                   \
-            return allox_fail((h), SW_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
 /* free_stride: ints between two instances' worker counts */
 int allox_run(sw_handle* h, const char* who, int32_t count, const int64_t* job_off,
               const int32_t* num_types, const int32_t* free_workers, int32_t free_stride,
               const double* p, const double* d, int32_t* job_worker, int32_t* job_position,
               int32_t* worker_first, const int64_t* wrk_off_in, double* costs) {
     const std::string n(who);
-    if (job_off[0] != 0) return allox_fail(h, SW_ERR_INVALID, n + ": job offsets must start at 0");
+    if (job_off[0] != 0) return sw_fail(h, SW_ERR_INVALID, n + ": job offsets must start at 0");
     if (wrk_off_in && wrk_off_in[0] != 0)
-        return allox_fail(h, SW_ERR_INVALID, n + ": worker offsets must start at 0");
+        return sw_fail(h, SW_ERR_INVALID, n + ": worker offsets must start at 0");
     const size_t C = (size_t)count;
     std::vector<int64_t> off_store(2 * C + 1, 0);
     int64_t* wrk_off = off_store.data();
@@ -251,20 +234,20 @@ int allox_run(sw_handle* h, const char* who, int32_t count, const int64_t* job_o
     wrk_off[0] = 0;
     for (int32_t i = 0; i < count; ++i) {
         const int64_t m = job_off[i + 1] - job_off[i];
-        if (m < 0) return allox_fail(h, SW_ERR_INVALID, n + ": job offsets must not decrease");
+        if (m < 0) return sw_fail(h, SW_ERR_INVALID, n + ": job offsets must not decrease");
         const int32_t T = num_types[i];
         if (T < 1 || T > SW_ALLOX_MAX_TYPES)
-            return allox_fail(h, SW_ERR_INVALID, n + ": num_types must be in [1, 8]");
+            return sw_fail(h, SW_ERR_INVALID, n + ": num_types must be in [1, 8]");
         int64_t nw = 0;
         for (int32_t t = 0; t < T; ++t) {
             const int32_t f = free_workers[(size_t)i * free_stride + t];
-            if (f < 0) return allox_fail(h, SW_ERR_INVALID, n + ": worker counts must be >= 0");
+            if (f < 0) return sw_fail(h, SW_ERR_INVALID, n + ": worker counts must be >= 0");
             nw += f;
         }
         if (wrk_off_in && wrk_off_in[i + 1] - wrk_off_in[i] != nw)
-            return allox_fail(h, SW_ERR_INVALID, n + ": worker offsets must step by the sum of the worker counts");
+            return sw_fail(h, SW_ERR_INVALID, n + ": worker offsets must step by the sum of the worker counts");
         if (m > SW_ALLOX_MAX_JOBS || nw > SW_ALLOX_MAX_WORKERS)
-            return allox_fail(h, SW_ERR_CAPACITY, n + ": more than 1024 jobs or 1024 free workers in one instance");
+            return sw_fail(h, SW_ERR_CAPACITY, n + ": more than 1024 jobs or 1024 free workers in one instance");
         wrk_off[i + 1] = wrk_off[i] + nw;
         p_off[i] = P;
         P += m * T;
@@ -278,14 +261,14 @@ int allox_run(sw_handle* h, const char* who, int32_t count, const int64_t* job_o
     }
     const int64_t M = job_off[count], W = wrk_off[count];
     if (M > 0 && (!p || !d || !job_worker || !job_position))
-        return allox_fail(h, SW_ERR_INVALID, n + ": null pointers");
-    if (W > 0 && !worker_first) return allox_fail(h, SW_ERR_INVALID, n + ": null pointers");
+        return sw_fail(h, SW_ERR_INVALID, n + ": null pointers");
+    if (W > 0 && !worker_first) return sw_fail(h, SW_ERR_INVALID, n + ": null pointers");
     for (int64_t k = 0; k < P; ++k)
         if (!(p[k] >= 0.0) || !(p[k] <= SW_ALLOX_PROC_MAX))
-            return allox_fail(h, SW_ERR_INVALID, n + ": processing times must be finite, >= 0 and <= 1e30");
+            return sw_fail(h, SW_ERR_INVALID, n + ": processing times must be finite, >= 0 and <= 1e30");
     for (int64_t j = 0; j < M; ++j)
         if (!(d[j] >= 0.0) || !(d[j] <= SW_ALLOX_DELAY_MAX))
-            return allox_fail(h, SW_ERR_INVALID, n + ": delays must be finite, >= 0 and <= 1e15");
+            return sw_fail(h, SW_ERR_INVALID, n + ": delays must be finite, >= 0 and <= 1e15");
     for (int64_t j = 0; j < M; ++j) { job_worker[j] = -1; job_position[j] = 0; }
     for (int64_t j = 0; j < W; ++j) worker_first[j] = -1;
     if (costs)
@@ -297,18 +280,17 @@ int allox_run(sw_handle* h, const char* who, int32_t count, const int64_t* job_o
     const char* ws_env = getenv("SW_ALLOX_WAVE_SLOTS");
     if (ws_env && ws_env[0]) wave_slots = atoi(ws_env);
 
-    ALLOX_HIP(h, hipSetDevice(h->device));
-    if (!h->allox) h->allox = new AlloxBufs();
-    AlloxBufs* b = (AlloxBufs*)h->allox;
+    SW_HIP(h, hipSetDevice(h->device));
+    sw_io_bufs* b = &h->io;
     const size_t Ms = (size_t)M, Ws = (size_t)W, Ps = (size_t)P;
     const size_t o_wo = (C + 1) * 8, o_po = o_wo + (C + 1) * 8, o_p = o_po + C * 8, o_d = o_p + Ps * 8,
                  o_f = o_d + Ms * 8, o_t = o_f + C * SW_ALLOX_MAX_TYPES * 4, in_bytes = o_t + C * 4;
     const size_t o_jw = C * 8, o_jp = o_jw + Ms * 4, o_wf = o_jp + Ms * 4, o_st = o_wf + Ws * 4,
                  out_bytes = o_st + C * 4;
-    ALLOX_HIP(h, b->in.reserve(in_bytes));
-    ALLOX_HIP(h, b->out.reserve(out_bytes));
-    ALLOX_HIP(h, b->hin.reserve(in_bytes));
-    ALLOX_HIP(h, b->hout.reserve(out_bytes));
+    SW_HIP(h, b->in.reserve(in_bytes));
+    SW_HIP(h, b->out.reserve(out_bytes));
+    SW_HIP(h, b->hin.reserve(in_bytes));
+    SW_HIP(h, b->hout.reserve(out_bytes));
     memcpy(b->hin.p, job_off, (C + 1) * 8);
     memcpy(b->hin.p + o_wo, wrk_off, (C + 1) * 8);
     memcpy(b->hin.p + o_po, p_off, C * 8);
@@ -319,7 +301,7 @@ int allox_run(sw_handle* h, const char* who, int32_t count, const int64_t* job_o
         for (int32_t t = 0; t < SW_ALLOX_MAX_TYPES; ++t)
             hf[i * SW_ALLOX_MAX_TYPES + t] = t < num_types[i] ? free_workers[i * free_stride + t] : 0;
     memcpy(b->hin.p + o_t, num_types, C * 4);
-    ALLOX_HIP(h, hipMemcpyAsync(b->in.p, b->hin.p, in_bytes, hipMemcpyHostToDevice, h->stream));
+    SW_HIP(h, hipMemcpyAsync(b->in.p, b->hin.p, in_bytes, hipMemcpyHostToDevice, h->stream));
     unsigned char* di = b->in.p;
     unsigned char* dout = b->out.p;
     if (max_slots <= wave_slots)
@@ -336,12 +318,12 @@ int allox_run(sw_handle* h, const char* who, int32_t count, const int64_t* job_o
                            (const double*)(di + o_d), (int32_t*)(dout + o_jw), (int32_t*)(dout + o_jp),
                            (int32_t*)(dout + o_wf), (double*)dout, (int32_t*)(dout + o_st),
                            stage ? (uint32_t)lds : 0u);
-    ALLOX_HIP(h, hipGetLastError());
-    ALLOX_HIP(h, hipMemcpyAsync(b->hout.p, b->out.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
-    ALLOX_HIP(h, hipStreamSynchronize(h->stream));
+    SW_HIP(h, hipGetLastError());
+    SW_HIP(h, hipMemcpyAsync(b->hout.p, b->out.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
+    SW_HIP(h, hipStreamSynchronize(h->stream));
     const int32_t* st = (const int32_t*)(b->hout.p + o_st);
     for (size_t i = 0; i < C; ++i)
-        if (st[i] != 0) return allox_fail(h, SW_ERR_INVALID, n + ": a search found no column");
+        if (st[i] != 0) return sw_fail(h, SW_ERR_INVALID, n + ": a search found no column");
     if (Ms) memcpy(job_worker, b->hout.p + o_jw, Ms * 4);
     if (Ms) memcpy(job_position, b->hout.p + o_jp, Ms * 4);
     if (Ws) memcpy(worker_first, b->hout.p + o_wf, Ws * 4);
@@ -351,23 +333,15 @@ int allox_run(sw_handle* h, const char* who, int32_t count, const int64_t* job_o
 
 }  // namespace
 
-void sw_allox_release(sw_handle* h) {
-    if (!h || !h->allox) return;
-    AlloxBufs* b = (AlloxBufs*)h->allox;
-    b->in.release(); b->out.release(); b->hin.release(); b->hout.release();
-    delete b;
-    h->allox = nullptr;
-}
-
 extern "C" int sw_allox_assign(sw_handle* h, int32_t num_jobs, int32_t num_types,
                                const int32_t* free_workers, const double* proc_time,
                                const double* delay, int32_t* job_worker, int32_t* job_position,
                                int32_t* worker_first, double* cost) {
     if (!h) return SW_ERR_INVALID;
-    if (num_jobs < 0) return allox_fail(h, SW_ERR_INVALID, "sw_allox_assign: num_jobs < 0");
+    if (num_jobs < 0) return sw_fail(h, SW_ERR_INVALID, "sw_allox_assign: num_jobs < 0");
     if (num_types < 1 || num_types > SW_ALLOX_MAX_TYPES)
-        return allox_fail(h, SW_ERR_INVALID, "sw_allox_assign: num_types must be in [1, 8]");
-    if (!free_workers) return allox_fail(h, SW_ERR_INVALID, "sw_allox_assign: null pointers");
+        return sw_fail(h, SW_ERR_INVALID, "sw_allox_assign: num_types must be in [1, 8]");
+    if (!free_workers) return sw_fail(h, SW_ERR_INVALID, "sw_allox_assign: null pointers");
     const int64_t offsets[2] = {0, num_jobs};
     return allox_run(h, "sw_allox_assign", 1, offsets, &num_types, free_workers, 0, proc_time, delay,
                      job_worker, job_position, worker_first, nullptr, cost);
@@ -381,7 +355,7 @@ extern "C" int sw_allox_assign_batch(sw_handle* h, int32_t count, const int64_t*
                                      double* costs) {
     if (!h) return SW_ERR_INVALID;
     if (count < 0 || (count > 0 && (!job_offsets || !num_types || !free_workers || !worker_offsets)))
-        return allox_fail(h, SW_ERR_INVALID, "sw_allox_assign_batch: bad count or null pointers");
+        return sw_fail(h, SW_ERR_INVALID, "sw_allox_assign_batch: bad count or null pointers");
     if (count == 0) return SW_OK;
     return allox_run(h, "sw_allox_assign_batch", count, job_offsets, num_types, free_workers,
                      SW_ALLOX_MAX_TYPES, proc_time, delay, job_worker, job_position, worker_first,

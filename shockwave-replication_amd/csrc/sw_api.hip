@@ -83,21 +83,6 @@ thread_local std::string g_create_error;
 
 namespace {
 
-int fail(sw_handle* h, int code, const std::string& msg) {
-    if (h) h->err = msg;
-    return code;
-}
-
-int hip_fail(sw_handle* h, hipError_t e, const char* what) {
-    return fail(h, SW_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
-#define SW_HIP(h, call)                                        \
-    do {                                                       \
-        hipError_t _e = (call);                                \
-        if (_e != hipSuccess) return hip_fail((h), _e, #call); \
-    } while (0)
-
 int collect_timing(sw_handle* h) {
     for (size_t i = 0; i < h->ev_used; ++i) {
         SW_HIP(h, hipEventSynchronize(h->ev_pool[2 * i + 1]));
@@ -226,11 +211,7 @@ void sw_destroy(sw_handle* h) {
     if (h->dn) (void)hipStreamSynchronize(h->dn);
     sw_shard_release(h);
     sw_mmf_release(h);
-    sw_ftf_release(h);
-    sw_wf_release(h);
-    sw_mtd_release(h);
-    sw_mst_release(h);
-    sw_allox_release(h);
+    sw_io_release(h);
     h->d_in.release(); h->d_res.release();
     h->d_ws_u8.release(); h->d_ws_u64.release(); h->d_ws_sort.release();
     h->d_ws_keys.release(); h->d_ws_jc.release(); h->d_stamps.release();
@@ -315,14 +296,14 @@ void par_instances(const sw_handle* h, int32_t lo, int32_t hi, F&& f) {
 /* Sizes and offsets of a batch from the problems' headers, capacity for it,
  * and no batch described until its upload completes. */
 int prepare_batch(sw_handle* h, int32_t count, const sw_problem* probs) {
-    if (count < 0 || (count > 0 && !probs)) return fail(h, SW_ERR_INVALID, "bad batch");
+    if (count < 0 || (count > 0 && !probs)) return sw_fail(h, SW_ERR_INVALID, "bad batch");
     SW_HIP(h, hipSetDevice(h->device));
     int64_t J = 0, P = 0;
     int32_t maxN = 0, maxT = 1;
     for (int32_t i = 0; i < count; ++i) {
         const sw_problem& pr = probs[i];
         if (pr.num_jobs < 0 || pr.future_rounds < 1 || pr.future_rounds > SW_MAX_ROUNDS)
-            return fail(h, SW_ERR_INVALID, "invalid problem at index " + std::to_string(i));
+            return sw_fail(h, SW_ERR_INVALID, "invalid problem at index " + std::to_string(i));
         J += pr.num_jobs;
         P += (int64_t)pr.num_jobs * pr.future_rounds;
         maxN = std::max(maxN, pr.num_jobs);
@@ -345,18 +326,18 @@ int prepare_batch(sw_handle* h, int32_t count, const sw_problem* probs) {
     if (h->d_in.reserve(inb) || h->d_res.reserve(resb) ||
         h->d_masks.reserve(Jz) || h->d_nb.reserve(Jz) || h->d_lvl.reserve(std::max(count, 1)) ||
         h->d_lws.reserve(Jz) || h->d_lwm.reserve(Jz) || h->d_lwa.reserve(std::max(count, 1)))
-        return fail(h, SW_ERR_HIP, "device allocation failed");
+        return sw_fail(h, SW_ERR_HIP, "device allocation failed");
     if (!sw_on_chip(maxN, maxT)) {
         const int KT = maxT <= 32 ? 32 : 64;
         if (h->d_ws_u8.reserve(Jz * SW_WS_U8) || h->d_ws_u64.reserve(Jz * SW_WS_U64 + (size_t)SW_WS_PAD_U64 * std::max(count, 1)) ||
             h->d_ws_sort.reserve(Jz * 4) || h->d_ws_keys.reserve(Jz * KT) ||
             h->d_ws_jc.reserve(Jz))
-            return fail(h, SW_ERR_HIP, "workspace allocation failed");
+            return sw_fail(h, SW_ERR_HIP, "workspace allocation failed");
     }
     if (h->d_p2ws.reserve(Jz * SW_P2X_ARR_BYTES))
-        return fail(h, SW_ERR_HIP, "P2 exchange workspace allocation failed");
+        return sw_fail(h, SW_ERR_HIP, "P2 exchange workspace allocation failed");
     if (h->h_in.reserve(inb) || h->h_res.reserve(resb) || h->h_masks.reserve(Jz))
-        return fail(h, SW_ERR_HIP, "pinned allocation failed");
+        return sw_fail(h, SW_ERR_HIP, "pinned allocation failed");
     set_views(h, std::max(count, 1), (int64_t)Jz, std::max<int64_t>(P, 1));
     h->inst.resize(count);
     h->Ns.resize(count);
@@ -385,7 +366,7 @@ int prepare_batch(sw_handle* h, int32_t count, const sw_problem* probs) {
  * current batch is touched, in parallel over equal instance ranges; the
  * error names the first invalid index. */
 int validate_all(sw_handle* h, const sw_problem* probs, int32_t count) {
-    if (count < 0 || (count > 0 && !probs)) return fail(h, SW_ERR_INVALID, "bad batch");
+    if (count < 0 || (count > 0 && !probs)) return sw_fail(h, SW_ERR_INVALID, "bad batch");
     std::atomic<int32_t> bad{INT32_MAX};
     auto check = [&](int32_t a, int32_t b) {
         for (int32_t i = a; i < b; ++i)
@@ -411,7 +392,7 @@ int validate_all(sw_handle* h, const sw_problem* probs, int32_t count) {
     check(0, nt > 1 ? (int32_t)((int64_t)count / nt) : count);
     for (auto& x : th) x.join();
     if (bad.load() != INT32_MAX)
-        return fail(h, SW_ERR_INVALID, "invalid problem at index " + std::to_string(bad.load()));
+        return sw_fail(h, SW_ERR_INVALID, "invalid problem at index " + std::to_string(bad.load()));
     return SW_OK;
 }
 
@@ -535,7 +516,7 @@ int launch(sw_handle* h, int32_t lo, int32_t hi, hipStream_t s, bool timed, bool
     B.fuse_p2x = one && (split || B.count <= fuse_max_count()); /* split: always fused */
     B.loop_split = split && B.count >= loop_min_count();
     hipError_t e = split ? sw_launch_split(&B, h->maxN, h->maxT, s) : sw_launch_plan(&B, h->maxN, h->maxT, s);
-    if (e != hipSuccess) return hip_fail(h, e, "plan kernel launch");
+    if (e != hipSuccess) return sw_fail(h, SW_ERR_HIP, std::string("plan kernel launch: ") + hipGetErrorString(e));
     if (timed) {
         SW_HIP(h, hipEventRecord(h->ev_pool[2 * h->ev_used + 1], s));
         SW_HIP(h, hipEventRecord(h->ev_p2x[2 * h->ev_used], s));
@@ -543,7 +524,7 @@ int launch(sw_handle* h, int32_t lo, int32_t hi, hipStream_t s, bool timed, bool
     /* the P2 exchange step (sw_p2x_kernel.hip) on the plan kernels' masks */
     if (!B.fuse_p2x) {
         e = sw_launch_p2x(&B, h->maxN, h->maxT, s);
-        if (e != hipSuccess) return hip_fail(h, e, "sw_p2x_kernel launch");
+        if (e != hipSuccess) return sw_fail(h, SW_ERR_HIP, std::string("sw_p2x_kernel launch: ") + hipGetErrorString(e));
     }
     if (timed) {
         SW_HIP(h, hipEventRecord(h->ev_p2x[2 * h->ev_used + 1], s));
@@ -756,7 +737,7 @@ int sw_batch_upload(sw_handle* h, int32_t count, const sw_problem* probs) {
     mark_loaded(h);
 #ifdef SW_STAMPS
     if (h->d_stamps.reserve((size_t)std::max(count, 1) * SW_STAMP_SLOTS))
-        return fail(h, SW_ERR_HIP, "stamp buffer allocation failed");
+        return sw_fail(h, SW_ERR_HIP, "stamp buffer allocation failed");
     SW_HIP(h, hipMemset(h->d_stamps.p, 0, (size_t)std::max(count, 1) * SW_STAMP_SLOTS * sizeof(uint64_t)));
 #endif
     return SW_OK;
@@ -774,7 +755,7 @@ int sw_debug_stamps(sw_handle* h, uint64_t* out) {
 
 int sw_batch_run(sw_handle* h) {
     if (!h) return SW_ERR_INVALID;
-    if (!h->loaded) return fail(h, SW_ERR_INVALID, "no batch uploaded");
+    if (!h->loaded) return sw_fail(h, SW_ERR_INVALID, "no batch uploaded");
     if (h->count <= 0) return SW_OK;
     SW_HIP(h, hipSetDevice(h->device));
     h->masks_valid = h->keep_masks;
@@ -791,12 +772,12 @@ int sw_batch_keep_masks(sw_handle* h, int32_t keep) {
 
 int sw_batch_download(sw_handle* h, sw_result* res) {
     if (!h) return SW_ERR_INVALID;
-    if (!h->loaded) return fail(h, SW_ERR_INVALID, "no batch uploaded");
-    if (h->count > 0 && !res) return fail(h, SW_ERR_INVALID, "null result array");
+    if (!h->loaded) return sw_fail(h, SW_ERR_INVALID, "no batch uploaded");
+    if (h->count > 0 && !res) return sw_fail(h, SW_ERR_INVALID, "null result array");
     SW_HIP(h, hipSetDevice(h->device));
     const Wants w = wants_of(res, h->count);
     if (w.masks && !h->masks_valid)
-        return fail(h, SW_ERR_INVALID, "plan_masks: the last sw_batch_run did not keep them (sw_batch_keep_masks)");
+        return sw_fail(h, SW_ERR_INVALID, "plan_masks: the last sw_batch_run did not keep them (sw_batch_keep_masks)");
     int rc = d2h(h, 0, h->count, h->stream, w);
     if (rc != SW_OK) return rc;
     SW_HIP(h, hipStreamSynchronize(h->stream));
@@ -806,7 +787,7 @@ int sw_batch_download(sw_handle* h, sw_result* res) {
 
 int sw_plan_solve_batch(sw_handle* h, int32_t count, const sw_problem* probs, sw_result* res) {
     if (!h) return SW_ERR_INVALID;
-    if (count > 0 && !res) return fail(h, SW_ERR_INVALID, "null result array");
+    if (count > 0 && !res) return sw_fail(h, SW_ERR_INVALID, "null result array");
 #ifndef SW_STAMPS
     /* the chunk pipeline for large on-chip batches on the handle's own
      * stream (a borrowed stream keeps every step on it) */

@@ -419,6 +419,40 @@ struct sw_blk_t {
         M = sw_f64u(mm);
     }
 
+    /* sw_detsum of the per-thread partials v, the max of a and the min of b, one
+     * barrier */
+    __device__ __forceinline__ void detsum_max_min(double v, double a, double b, double& S, double& A,
+                                                   double& B) {
+        v = wave_dettree(v);
+        a = wave_max_f64(a);
+        b = wave_min_f64(b);
+        if (lane_id() == 0) {
+            X->d[par][wave_id()][0] = v;
+            X->u2[par][wave_id()][0] = __builtin_bit_cast(uint64_t, a);
+            X->u2[par][wave_id()][1] = __builtin_bit_cast(uint64_t, b);
+        }
+        __syncthreads();
+        double s[NW];
+        double am = __builtin_bit_cast(double, X->u2[par][0][0]);
+        double bm = __builtin_bit_cast(double, X->u2[par][0][1]);
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            s[w] = X->d[par][w][0];
+            const double aw = __builtin_bit_cast(double, X->u2[par][w][0]);
+            const double bw = __builtin_bit_cast(double, X->u2[par][w][1]);
+            am = aw > am ? aw : am;
+            bm = bw < bm ? bw : bm;
+        }
+#pragma unroll
+        for (int h = NW / 2; h >= 1; h >>= 1)
+#pragma unroll
+            for (int i = 0; i < h; ++i) s[i] = s[i] + s[i + h];
+        flip();
+        S = sw_f64u(s[0]);
+        A = sw_f64u(am);
+        B = sw_f64u(bm);
+    }
+
     /* sw_detsum of a and of b, the max of m ≥ 0 and the sum of the small
      * counts c, one barrier (the emit's four results) */
     __device__ __forceinline__ void detsum2_max_cnt(double a, double b, double m, int32_t c,

@@ -57,6 +57,15 @@ struct HostBuf {
     }
 };
 
+/* One input block and one output block per call, and their pinned mirrors: one
+ * copy each way.  The per-job allocation policies (sw_alloc.h) and AlloX share
+ * the set: each of their calls ends in a stream synchronise, so no two are in
+ * flight on one handle, and reserve only grows. */
+struct sw_io_bufs {
+    DevBuf<unsigned char> in, out;
+    HostBuf<unsigned char> hin, hout;
+};
+
 struct sw_handle {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -127,30 +136,29 @@ struct sw_handle {
     sw_shard_state* shard = nullptr;
     /* MaxMinFairness allocation buffers (sw_mmf.hip) */
     void* mmf = nullptr;
-    /* FinishTimeFairness allocation buffers (sw_ftf.hip) */
-    void* ftf = nullptr;
-    /* water-filling MaxMinFairness allocation buffers (sw_wf.hip) */
-    void* wf = nullptr;
-    /* MinTotalDuration allocation buffers (sw_mtd.hip) */
-    void* mtd = nullptr;
-    /* max-sum-throughput allocation buffers (sw_mst.hip) */
-    void* mst = nullptr;
-    /* AlloX assignment buffers (sw_allox.hip) */
-    void* allox = nullptr;
+    /* the blocks of the per-job allocation policies (sw_alloc.h) and of AlloX (sw_allox.hip) */
+    sw_io_bufs io;
 };
+
+/* records a call's error text in the handle; SW_HIP does so for a failed HIP call */
+inline int sw_fail(sw_handle* h, int code, const std::string& msg) {
+    if (h) h->err = msg;
+    return code;
+}
+
+#define SW_HIP(h, call)                                                                     \
+    do {                                                                                    \
+        hipError_t _e = (call);                                                             \
+        if (_e != hipSuccess)                                                               \
+            return sw_fail((h), SW_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_e)); \
+    } while (0)
 
 /* sw_shard.hip: frees the sharded-mode state and communicator */
 void sw_shard_release(sw_handle* h);
 /* sw_mmf.hip: frees the MaxMinFairness buffers */
 void sw_mmf_release(sw_handle* h);
-/* sw_ftf.hip: frees the FinishTimeFairness buffers */
-void sw_ftf_release(sw_handle* h);
-/* sw_wf.hip: frees the water-filling buffers */
-void sw_wf_release(sw_handle* h);
-/* sw_mtd.hip: frees the MinTotalDuration buffers */
-void sw_mtd_release(sw_handle* h);
-/* sw_mst.hip: frees the max-sum-throughput buffers */
-void sw_mst_release(sw_handle* h);
-/* sw_allox.hip: frees the AlloX buffers */
-void sw_allox_release(sw_handle* h);
+/* frees the shared input / output blocks */
+inline void sw_io_release(sw_handle* h) {
+    h->io.in.release(); h->io.out.release(); h->io.hin.release(); h->io.hout.release();
+}
 

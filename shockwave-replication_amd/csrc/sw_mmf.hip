@@ -246,18 +246,6 @@ struct MmfBufs {
     HostBuf<double> hlc, hlx, hlout;
 };
 
-int mmf_fail(sw_handle* h, int code, const std::string& msg) {
-    h->err = msg;
-    return code;
-}
-
-#define MMF_HIP(h, call)                                                                     \
-    do {                                                                                     \
-        hipError_t _e = (call);                                                              \
-        if (_e != hipSuccess)                                                                \
-            return mmf_fail((h), SW_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
 }  // namespace
 
 void sw_mmf_release(sw_handle* h) {
@@ -278,42 +266,42 @@ extern "C" int sw_mmf_allocate(sw_handle* h, int32_t num_jobs, int32_t num_worke
     if (!h) return SW_ERR_INVALID;
     if (num_jobs < 0 || num_workers <= 0 || (num_jobs > 0 && (!scale_factors || !coefficients ||
                                                               !allocation)))
-        return mmf_fail(h, SW_ERR_INVALID, "sw_mmf_allocate: bad sizes or null pointers");
+        return sw_fail(h, SW_ERR_INVALID, "sw_mmf_allocate: bad sizes or null pointers");
     for (int32_t j = 0; j < num_jobs; ++j) {
         const double c = coefficients[j];
         if (scale_factors[j] < 1 || scale_factors[j] > SW_MAX_WIDTH || !(c > 0.0) || !isfinite(c))
-            return mmf_fail(h, SW_ERR_INVALID,
+            return sw_fail(h, SW_ERR_INVALID,
                             "sw_mmf_allocate: scale factors must be in [1,255] and "
                             "coefficients finite and > 0");
     }
     if (level) { level[0] = 0.0; level[1] = 0.0; }
     if (num_jobs == 0) return SW_OK; /* policy.flatten returns None (policy.py:20-22) */
-    MMF_HIP(h, hipSetDevice(h->device));
+    SW_HIP(h, hipSetDevice(h->device));
     if (!h->mmf) h->mmf = new MmfBufs();
     MmfBufs* b = (MmfBufs*)h->mmf;
     const size_t n = (size_t)num_jobs;
-    MMF_HIP(h, b->sf.reserve(n));
-    MMF_HIP(h, b->c.reserve(n));
-    MMF_HIP(h, b->x.reserve(n));
-    MMF_HIP(h, b->out.reserve(2));
-    MMF_HIP(h, b->hsf.reserve(n));
-    MMF_HIP(h, b->hc.reserve(n));
-    MMF_HIP(h, b->hx.reserve(n));
-    MMF_HIP(h, b->hout.reserve(2));
+    SW_HIP(h, b->sf.reserve(n));
+    SW_HIP(h, b->c.reserve(n));
+    SW_HIP(h, b->x.reserve(n));
+    SW_HIP(h, b->out.reserve(2));
+    SW_HIP(h, b->hsf.reserve(n));
+    SW_HIP(h, b->hc.reserve(n));
+    SW_HIP(h, b->hx.reserve(n));
+    SW_HIP(h, b->hout.reserve(2));
     memcpy(b->hsf.p, scale_factors, n * sizeof(int32_t));
     memcpy(b->hc.p, coefficients, n * sizeof(double));
-    MMF_HIP(h, hipMemcpyAsync(b->sf.p, b->hsf.p, n * sizeof(int32_t), hipMemcpyHostToDevice,
+    SW_HIP(h, hipMemcpyAsync(b->sf.p, b->hsf.p, n * sizeof(int32_t), hipMemcpyHostToDevice,
                               h->stream));
-    MMF_HIP(h, hipMemcpyAsync(b->c.p, b->hc.p, n * sizeof(double), hipMemcpyHostToDevice,
+    SW_HIP(h, hipMemcpyAsync(b->c.p, b->hc.p, n * sizeof(double), hipMemcpyHostToDevice,
                               h->stream));
     hipLaunchKernelGGL(sw_mmf_kernel, dim3(1), dim3(SW_BLOCK), 0, h->stream, num_jobs,
                        num_workers, b->sf.p, b->c.p, b->x.p, b->out.p);
-    MMF_HIP(h, hipGetLastError());
-    MMF_HIP(h, hipMemcpyAsync(b->hx.p, b->x.p, n * sizeof(double), hipMemcpyDeviceToHost,
+    SW_HIP(h, hipGetLastError());
+    SW_HIP(h, hipMemcpyAsync(b->hx.p, b->x.p, n * sizeof(double), hipMemcpyDeviceToHost,
                               h->stream));
-    MMF_HIP(h, hipMemcpyAsync(b->hout.p, b->out.p, 2 * sizeof(double), hipMemcpyDeviceToHost,
+    SW_HIP(h, hipMemcpyAsync(b->hout.p, b->out.p, 2 * sizeof(double), hipMemcpyDeviceToHost,
                               h->stream));
-    MMF_HIP(h, hipStreamSynchronize(h->stream));
+    SW_HIP(h, hipStreamSynchronize(h->stream));
     memcpy(allocation, b->hx.p, n * sizeof(double));
     if (level) { level[0] = b->hout.p[0]; level[1] = b->hout.p[1]; }
     return SW_OK;
@@ -325,17 +313,17 @@ extern "C" int sw_mmf_allocate_types(sw_handle* h, int32_t num_jobs, int32_t num
     if (!h) return SW_ERR_INVALID;
     if (num_jobs < 0 || num_jobs > SW_LP_MAX_JOBS || num_types < 1 || num_types > SW_LP_MAX_TYPES ||
         !workers || (num_jobs > 0 && (!scale_factors || !coefficients || !allocation)))
-        return mmf_fail(h, SW_ERR_INVALID, "sw_mmf_allocate_types: bad sizes or null pointers");
+        return sw_fail(h, SW_ERR_INVALID, "sw_mmf_allocate_types: bad sizes or null pointers");
     for (int32_t k = 0; k < num_types; ++k)
         if (workers[k] < 0)
-            return mmf_fail(h, SW_ERR_INVALID, "sw_mmf_allocate_types: worker counts must be >= 0");
+            return sw_fail(h, SW_ERR_INVALID, "sw_mmf_allocate_types: worker counts must be >= 0");
     for (int32_t j = 0; j < num_jobs; ++j) {
         if (scale_factors[j] < 1 || scale_factors[j] > SW_MAX_WIDTH)
-            return mmf_fail(h, SW_ERR_INVALID, "sw_mmf_allocate_types: scale factors must be in [1,255]");
+            return sw_fail(h, SW_ERR_INVALID, "sw_mmf_allocate_types: scale factors must be in [1,255]");
         for (int32_t k = 0; k < num_types; ++k) {
             const double c = coefficients[(size_t)j * num_types + k];
             if (!(c >= 0.0) || !isfinite(c))
-                return mmf_fail(h, SW_ERR_INVALID,
+                return sw_fail(h, SW_ERR_INVALID,
                                 "sw_mmf_allocate_types: coefficients must be finite and >= 0");
         }
     }
@@ -344,38 +332,38 @@ extern "C" int sw_mmf_allocate_types(sw_handle* h, int32_t num_jobs, int32_t num
     const sw_lp_dims d = sw_lp_dims_of(num_jobs, num_types);
     const size_t cells = (size_t)(d.R + 1) * (size_t)d.W;
     if (cells * sizeof(double) > ((size_t)1 << 28))
-        return mmf_fail(h, SW_ERR_CAPACITY, "sw_mmf_allocate_types: tableau above 256 MB");
-    MMF_HIP(h, hipSetDevice(h->device));
+        return sw_fail(h, SW_ERR_CAPACITY, "sw_mmf_allocate_types: tableau above 256 MB");
+    SW_HIP(h, hipSetDevice(h->device));
     if (!h->mmf) h->mmf = new MmfBufs();
     MmfBufs* b = (MmfBufs*)h->mmf;
     const size_t m = (size_t)num_jobs, mn = m * (size_t)num_types;
-    MMF_HIP(h, b->lw.reserve((size_t)num_types));
-    MMF_HIP(h, b->lsf.reserve(m));
-    MMF_HIP(h, b->lc.reserve(mn));
-    MMF_HIP(h, b->lx.reserve(mn));
-    MMF_HIP(h, b->lout.reserve(4));
-    MMF_HIP(h, b->tab.reserve(cells));
-    MMF_HIP(h, b->lbasis.reserve((size_t)d.R));
-    MMF_HIP(h, b->lf.reserve((size_t)d.R + 1));
-    MMF_HIP(h, b->lp.reserve((size_t)d.W));
-    MMF_HIP(h, b->lst.reserve(1));
-    MMF_HIP(h, b->hlst.reserve(1));
-    MMF_HIP(h, b->hlw.reserve((size_t)num_types));
-    MMF_HIP(h, b->hlsf.reserve(m));
-    MMF_HIP(h, b->hlc.reserve(mn));
-    MMF_HIP(h, b->hlx.reserve(mn));
-    MMF_HIP(h, b->hlout.reserve(4));
+    SW_HIP(h, b->lw.reserve((size_t)num_types));
+    SW_HIP(h, b->lsf.reserve(m));
+    SW_HIP(h, b->lc.reserve(mn));
+    SW_HIP(h, b->lx.reserve(mn));
+    SW_HIP(h, b->lout.reserve(4));
+    SW_HIP(h, b->tab.reserve(cells));
+    SW_HIP(h, b->lbasis.reserve((size_t)d.R));
+    SW_HIP(h, b->lf.reserve((size_t)d.R + 1));
+    SW_HIP(h, b->lp.reserve((size_t)d.W));
+    SW_HIP(h, b->lst.reserve(1));
+    SW_HIP(h, b->hlst.reserve(1));
+    SW_HIP(h, b->hlw.reserve((size_t)num_types));
+    SW_HIP(h, b->hlsf.reserve(m));
+    SW_HIP(h, b->hlc.reserve(mn));
+    SW_HIP(h, b->hlx.reserve(mn));
+    SW_HIP(h, b->hlout.reserve(4));
     memcpy(b->hlw.p, workers, (size_t)num_types * sizeof(int32_t));
     memcpy(b->hlsf.p, scale_factors, m * sizeof(int32_t));
     memcpy(b->hlc.p, coefficients, mn * sizeof(double));
     hipStream_t st = h->stream;
-    MMF_HIP(h, hipMemcpyAsync(b->lw.p, b->hlw.p, (size_t)num_types * 4, hipMemcpyHostToDevice, st));
-    MMF_HIP(h, hipMemcpyAsync(b->lsf.p, b->hlsf.p, m * 4, hipMemcpyHostToDevice, st));
-    MMF_HIP(h, hipMemcpyAsync(b->lc.p, b->hlc.p, mn * 8, hipMemcpyHostToDevice, st));
+    SW_HIP(h, hipMemcpyAsync(b->lw.p, b->hlw.p, (size_t)num_types * 4, hipMemcpyHostToDevice, st));
+    SW_HIP(h, hipMemcpyAsync(b->lsf.p, b->hlsf.p, m * 4, hipMemcpyHostToDevice, st));
+    SW_HIP(h, hipMemcpyAsync(b->lc.p, b->hlc.p, mn * 8, hipMemcpyHostToDevice, st));
     const unsigned gi = (unsigned)std::min<size_t>((cells + kLpTB - 1) / kLpTB, 4096);
     hipLaunchKernelGGL(k_lp_init, dim3(gi), dim3(kLpTB), 0, st, num_jobs, num_types, b->lw.p, b->lsf.p, b->lc.p,
                        b->tab.p, b->lbasis.p, b->lst.p);
-    MMF_HIP(h, hipGetLastError());
+    SW_HIP(h, hipGetLastError());
     /* pivots in chunks, the done flag read between them */
     constexpr int kChunk = 32;
     const int64_t maxp = sw_lp_max_pivots(&d);
@@ -386,20 +374,20 @@ extern "C" int sw_mmf_allocate_types(sw_handle* h, int32_t num_jobs, int32_t num
             hipLaunchKernelGGL(k_lp_update, dim3((unsigned)(d.R + 1)), dim3(kLpTB), 0, st, num_jobs, num_types,
                                b->tab.p, b->lf.p, b->lp.p, b->lst.p);
         }
-        MMF_HIP(h, hipGetLastError());
-        MMF_HIP(h, hipMemcpyAsync(b->hlst.p, b->lst.p, sizeof(LpState), hipMemcpyDeviceToHost, st));
-        MMF_HIP(h, hipStreamSynchronize(st));
+        SW_HIP(h, hipGetLastError());
+        SW_HIP(h, hipMemcpyAsync(b->hlst.p, b->lst.p, sizeof(LpState), hipMemcpyDeviceToHost, st));
+        SW_HIP(h, hipStreamSynchronize(st));
         if (b->hlst.p->done != 0 || done_piv > maxp) break;
     }
     hipLaunchKernelGGL(k_lp_result, dim3(1), dim3(SW_BLOCK), 0, st, num_jobs, num_types, b->tab.p, b->lbasis.p,
                        b->lst.p, b->lx.p, b->lout.p);
-    MMF_HIP(h, hipGetLastError());
-    MMF_HIP(h, hipMemcpyAsync(b->hlx.p, b->lx.p, mn * 8, hipMemcpyDeviceToHost, st));
-    MMF_HIP(h, hipMemcpyAsync(b->hlout.p, b->lout.p, 3 * 8, hipMemcpyDeviceToHost, st));
-    MMF_HIP(h, hipStreamSynchronize(st));
+    SW_HIP(h, hipGetLastError());
+    SW_HIP(h, hipMemcpyAsync(b->hlx.p, b->lx.p, mn * 8, hipMemcpyDeviceToHost, st));
+    SW_HIP(h, hipMemcpyAsync(b->hlout.p, b->lout.p, 3 * 8, hipMemcpyDeviceToHost, st));
+    SW_HIP(h, hipStreamSynchronize(st));
     const int status = (int)b->hlout.p[2];
     if (status != 0)
-        return mmf_fail(h, SW_ERR_CAPACITY,
+        return sw_fail(h, SW_ERR_CAPACITY,
                         status == -3 ? "sw_mmf_allocate_types: pivot cap reached"
                                      : "sw_mmf_allocate_types: no leaving row (unbounded)");
     memcpy(allocation, b->hlx.p, mn * sizeof(double));

@@ -37,14 +37,9 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <string>
 
 #include "../../include/shockwave_amd.h"
-#include "sw_block.h"
-#include "sw_handle.h"
+#include "sw_alloc.h"
 #include "sw_mst.h"
 
 #define SW_MST_LDS_JOBS 3072 /* 60 KB of dynamic LDS: with the exchange slots, inside the 64 KB a launch gets without opting in */
@@ -52,9 +47,9 @@
 
 namespace {
 
-/* The inputs of one instance: job lo + k of thread L is element
- * k·ks + L·ls — (1, q) in global memory, (512, 1) in the LDS image.  dw is the
- * density in the LDS image and the weight in global memory. */
+/* The inputs of one instance, in global memory or in the LDS image: job lo + k
+ * of the thread is element at(k) (sw_chunk_at).  dw is the density in the LDS
+ * image and the weight in global memory. */
 template <bool LDS>
 struct MstIn {
     const double* dw;
@@ -62,50 +57,12 @@ struct MstIn {
     const int32_t* sf;
     int32_t q;
     int32_t dropped;
-    __device__ __forceinline__ int32_t at(int32_t k) const {
-        return LDS ? k * SW_BLOCK + (int32_t)threadIdx.x : (int32_t)threadIdx.x * q + k;
-    }
+    __device__ __forceinline__ int32_t at(int32_t k) const { return sw_chunk_at<LDS>(k, q); }
     __device__ __forceinline__ double dens(int32_t i, double sf_) const {
         return LDS ? dw[i] : sw_mst_density(dw[i], sf_);
     }
     __device__ __forceinline__ double floor_(int32_t i) const { return sw_mst_floor(l[i], dropped); }
 };
-
-/* sw_detsum of the per-thread partials v, the max of a and the min of b, one
- * barrier */
-__device__ __forceinline__ void mst_sum_max_min(sw_blk& blk, double v, double a, double b, double& S,
-                                                double& A, double& B) {
-    sw_xchg* X = blk.X;
-    const int par = blk.par;
-    v = wave_dettree(v);
-    a = wave_max_f64(a);
-    b = wave_min_f64(b);
-    if (lane_id() == 0) {
-        X->d[par][wave_id()][0] = v;
-        X->u2[par][wave_id()][0] = __builtin_bit_cast(uint64_t, a);
-        X->u2[par][wave_id()][1] = __builtin_bit_cast(uint64_t, b);
-    }
-    __syncthreads();
-    double s[SW_WAVES];
-    double am = __builtin_bit_cast(double, X->u2[par][0][0]);
-    double bm = __builtin_bit_cast(double, X->u2[par][0][1]);
-#pragma unroll
-    for (int w = 0; w < SW_WAVES; ++w) {
-        s[w] = X->d[par][w][0];
-        const double aw = __builtin_bit_cast(double, X->u2[par][w][0]);
-        const double bw = __builtin_bit_cast(double, X->u2[par][w][1]);
-        am = aw > am ? aw : am;
-        bm = bw < bm ? bw : bm;
-    }
-#pragma unroll
-    for (int h = SW_WAVES / 2; h >= 1; h >>= 1)
-#pragma unroll
-        for (int i = 0; i < h; ++i) s[i] = s[i] + s[i + h];
-    blk.flip();
-    S = sw_f64u(s[0]);
-    A = sw_f64u(am);
-    B = sw_f64u(bm);
-}
 
 /* Σ_j sf_j·x_j(λ, m) over the thread's chunk */
 template <bool LDS>
@@ -138,7 +95,7 @@ __device__ __forceinline__ void mst_solve(sw_blk& blk, MstIn<LDS>& in, int32_t c
         dhi = d > dhi ? d : dhi;
     }
     double S, maxl, mind;
-    mst_sum_max_min(blk, c, ml, dlo, S, maxl, mind);
+    blk.detsum_max_min(c, ml, dlo, S, maxl, mind);
     const double maxd = blk.dmax(dhi);
     in.dropped = (maxl > 1.0 || S > Gd) ? 1 : 0;
 
@@ -168,7 +125,7 @@ __device__ __forceinline__ void mst_solve(sw_blk& blk, MstIn<LDS>& in, int32_t c
                 if (above) b = d < b ? d : b; else a = d > a ? d : a;
             }
             double F, A, B;
-            mst_sum_max_min(blk, c, a, b, F, A, B);
+            blk.detsum_max_min(c, a, b, F, A, B);
             if (F <= Gd) bhi = A >= 0.0 ? sw_bits(A) : bmid;
             else blo = B < inf ? sw_bits(B) - 1 : bmid;
         }
@@ -224,19 +181,13 @@ __global__ __launch_bounds__(SW_BLOCK) void sw_mst_kernel(const int64_t* __restr
     extern __shared__ double mst_lds[];
     __shared__ sw_xchg X;
     sw_blk blk{&X, 0};
-    const int64_t inst = blockIdx.x;
-    const int64_t base = offsets[inst];
-    const int32_t N = (int32_t)(offsets[inst + 1] - base);
-    double* out = levels + 4 * inst;
-    if (N <= 0) { /* an empty instance (policy.flatten returns None) */
-        if (threadIdx.x == 0) { out[0] = 0.0; out[1] = 0.0; out[2] = 0.0; out[3] = 0.0; }
-        return;
-    }
-    const int32_t G = workers[inst];
-    const int32_t q = (N + SW_BLOCK - 1) / SW_BLOCK;
-    const int32_t lo = (int32_t)threadIdx.x * q;
-    const int32_t hi = lo + q < N ? lo + q : N;
-    const int32_t cnt = hi > lo ? hi - lo : 0;
+    sw_chunk ch = sw_chunk_of(offsets);
+    double* out = levels + 4 * (int64_t)blockIdx.x;
+    if (ch.N <= 0) { sw_chunk_zero<4>(out); return; }
+    ch.split();
+    const int32_t G = workers[blockIdx.x];
+    const int64_t base = ch.base;
+    const int32_t q = ch.q, lo = ch.lo, cnt = ch.cnt;
     double* xo = x + base + lo;
     const double* wo = w + base + lo;
 
@@ -259,103 +210,35 @@ __global__ __launch_bounds__(SW_BLOCK) void sw_mst_kernel(const int64_t* __restr
     }
 }
 
-/* One input block and one output block per call (one copy each way):
- *   in : offsets[count+1] (int64) | w [total] | l [total] (double) | sf [total],
- *        workers [count] (int32)
- *   out: x [total] | levels [count][4] (double) */
-struct MstBufs {
-    DevBuf<unsigned char> in, out;
-    HostBuf<unsigned char> hin, hout;
-};
-
-int mst_fail(sw_handle* h, int code, const std::string& msg) {
-    h->err = msg;
-    return code;
-}
-
-#define MST_HIP(h, call)                                                                     \
-    do {                                                                                     \
-        hipError_t _e = (call);                                                              \
-        if (_e != hipSuccess)                                                                \
-            return mst_fail((h), SW_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
 int mst_run(sw_handle* h, const char* who, int32_t count, const int64_t* offsets, const int32_t* workers,
             const int32_t* sf, const double* w, const double* l, double* x, double* levels) {
-    const std::string n(who);
-    if (offsets[0] != 0) return mst_fail(h, SW_ERR_INVALID, n + ": offsets must start at 0");
-    int32_t maxq = 0;
-    for (int32_t i = 0; i < count; ++i) {
-        const int64_t nj = offsets[i + 1] - offsets[i];
-        if (nj < 0 || nj > (int64_t)INT32_MAX - SW_BLOCK)
-            return mst_fail(h, SW_ERR_INVALID, n + ": offsets must not decrease");
-        if (workers[i] < 1) return mst_fail(h, SW_ERR_INVALID, n + ": worker counts must be >= 1");
-        const int32_t q = (int32_t)((nj + SW_BLOCK - 1) / SW_BLOCK);
-        if (q * SW_BLOCK <= SW_MST_LDS_JOBS && q > maxq) maxq = q;
-    }
-    /* SW_MST_LDS=0: every instance on the global path (A/B timing, tools/mst_timing.py) */
-    const char* lds_env = getenv("SW_MST_LDS");
-    if (lds_env && lds_env[0] == '0') maxq = 0;
-    const int64_t total = offsets[count];
-    if (total > 0 && (!sf || !w || !x)) return mst_fail(h, SW_ERR_INVALID, n + ": null pointers");
-    for (int64_t j = 0; j < total; ++j) {
-        if (sf[j] < 1 || sf[j] > SW_MAX_WIDTH)
-            return mst_fail(h, SW_ERR_INVALID, n + ": scale factors must be in [1,255]");
-        if (!(w[j] >= 0.0) || !(w[j] <= SW_MST_WEIGHT_MAX))
-            return mst_fail(h, SW_ERR_INVALID, n + ": weights must be finite, >= 0 and <= 1e30");
-        if (l && !(l[j] >= 0.0))
-            return mst_fail(h, SW_ERR_INVALID, n + ": floors must be >= 0 (+inf allowed) and not NaN");
-    }
-    if (levels)
-        for (int64_t i = 0; i < 4 * (int64_t)count; ++i) levels[i] = 0.0;
-    if (total == 0) return SW_OK; /* only empty instances */
-    MST_HIP(h, hipSetDevice(h->device));
-    if (!h->mst) h->mst = new MstBufs();
-    MstBufs* b = (MstBufs*)h->mst;
-    const size_t T = (size_t)total, C = (size_t)count;
-    const size_t o_w = (C + 1) * 8, o_l = o_w + T * 8, o_sf = o_l + T * 8, o_g = o_sf + T * 4,
-                 in_bytes = o_g + C * 4;
-    const size_t o_lv = T * 8, out_bytes = o_lv + C * 32;
-    MST_HIP(h, b->in.reserve(in_bytes));
-    MST_HIP(h, b->out.reserve(out_bytes));
-    MST_HIP(h, b->hin.reserve(in_bytes));
-    MST_HIP(h, b->hout.reserve(out_bytes));
-    memcpy(b->hin.p, offsets, (C + 1) * 8);
-    memcpy(b->hin.p + o_w, w, T * 8);
-    if (l) memcpy(b->hin.p + o_l, l, T * 8);
-    else memset(b->hin.p + o_l, 0, T * 8); /* null floors: all zero */
-    memcpy(b->hin.p + o_sf, sf, T * 4);
-    memcpy(b->hin.p + o_g, workers, C * 4);
-    MST_HIP(h, hipMemcpyAsync(b->in.p, b->hin.p, in_bytes, hipMemcpyHostToDevice, h->stream));
-    unsigned char* d = b->in.p;
-    const size_t lds = (size_t)maxq * SW_BLOCK * SW_MST_JOB_BYTES;
-    hipLaunchKernelGGL(sw_mst_kernel, dim3((unsigned)count), dim3(SW_BLOCK), lds, h->stream,
-                       (const int64_t*)d, (const int32_t*)(d + o_g), (const int32_t*)(d + o_sf),
-                       (const double*)(d + o_w), (const double*)(d + o_l), (double*)b->out.p,
-                       (double*)(b->out.p + o_lv), maxq);
-    MST_HIP(h, hipGetLastError());
-    MST_HIP(h, hipMemcpyAsync(b->hout.p, b->out.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
-    MST_HIP(h, hipStreamSynchronize(h->stream));
-    memcpy(x, b->hout.p, T * 8);
-    if (levels) memcpy(levels, b->hout.p + o_lv, C * 32);
-    return SW_OK;
+    /* SW_MST_LDS=0: every instance on the global path (A/B timing, tools/mst_timing.py);
+     * null floors are optional: all zero */
+    const sw_alloc_call call{who, count, offsets, workers, "worker counts must be >= 1", 3,
+                             {{w, 8}, {l, 8, true}, {sf, 4}},
+                             x, levels, 4, SW_MST_LDS_JOBS, SW_MST_JOB_BYTES, "SW_MST_LDS"};
+    return sw_alloc_run(
+        h, call,
+        [=](int64_t j) -> const char* {
+            if (sf[j] < 1 || sf[j] > SW_MAX_WIDTH) return "scale factors must be in [1,255]";
+            if (!(w[j] >= 0.0) || !(w[j] <= SW_MST_WEIGHT_MAX)) return "weights must be finite, >= 0 and <= 1e30";
+            if (l && !(l[j] >= 0.0)) return "floors must be >= 0 (+inf allowed) and not NaN";
+            return nullptr;
+        },
+        [](const sw_alloc_dev& d) {
+            hipLaunchKernelGGL(sw_mst_kernel, dim3(d.count), dim3(SW_BLOCK), d.lds, d.stream, d.offsets, d.workers,
+                               (const int32_t*)d.col[2], (const double*)d.col[0], (const double*)d.col[1], d.x,
+                               d.levels, d.maxq);
+        });
 }
 
 }  // namespace
-
-void sw_mst_release(sw_handle* h) {
-    if (!h || !h->mst) return;
-    MstBufs* b = (MstBufs*)h->mst;
-    b->in.release(); b->out.release(); b->hin.release(); b->hout.release();
-    delete b;
-    h->mst = nullptr;
-}
 
 extern "C" int sw_mst_allocate(sw_handle* h, int32_t num_jobs, int32_t num_workers,
                                const int32_t* scale_factors, const double* weights,
                                const double* floors, double* allocation, double* level) {
     if (!h) return SW_ERR_INVALID;
-    if (num_jobs < 0) return mst_fail(h, SW_ERR_INVALID, "sw_mst_allocate: num_jobs < 0");
+    if (num_jobs < 0) return sw_fail(h, SW_ERR_INVALID, "sw_mst_allocate: num_jobs < 0");
     const int64_t offsets[2] = {0, num_jobs};
     return mst_run(h, "sw_mst_allocate", 1, offsets, &num_workers, scale_factors, weights, floors,
                    allocation, level);
@@ -367,7 +250,7 @@ extern "C" int sw_mst_allocate_batch(sw_handle* h, int32_t count, const int64_t*
                                      double* levels) {
     if (!h) return SW_ERR_INVALID;
     if (count < 0 || (count > 0 && (!offsets || !num_workers)))
-        return mst_fail(h, SW_ERR_INVALID, "sw_mst_allocate_batch: bad count or null pointers");
+        return sw_fail(h, SW_ERR_INVALID, "sw_mst_allocate_batch: bad count or null pointers");
     if (count == 0) return SW_OK;
     return mst_run(h, "sw_mst_allocate_batch", count, offsets, num_workers, scale_factors, weights,
                    floors, allocation, levels);

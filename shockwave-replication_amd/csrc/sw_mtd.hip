@@ -33,14 +33,9 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <string>
 
 #include "../../include/shockwave_amd.h"
-#include "sw_block.h"
-#include "sw_handle.h"
+#include "sw_alloc.h"
 #include "sw_mtd.h"
 
 #define SW_MTD_LDS_JOBS 4096 /* 48 KB of dynamic LDS: below the 64 KB a launch gets without opting in */
@@ -48,16 +43,14 @@
 
 namespace {
 
-/* The inputs of one instance: job lo + k of thread L is element
- * k·ks + L·ls — (1, q) in global memory, (512, 1) in the LDS image. */
+/* The inputs of one instance, in global memory or in the LDS image: job lo + k
+ * of the thread is element at(k) (sw_chunk_at). */
 template <bool LDS>
 struct MtdIn {
     const double* p;
     const int32_t* sf;
     int32_t q;
-    __device__ __forceinline__ int32_t at(int32_t k) const {
-        return LDS ? k * SW_BLOCK + (int32_t)threadIdx.x : (int32_t)threadIdx.x * q + k;
-    }
+    __device__ __forceinline__ int32_t at(int32_t k) const { return sw_chunk_at<LDS>(k, q); }
 };
 
 template <bool LDS>
@@ -135,19 +128,13 @@ __global__ __launch_bounds__(SW_BLOCK) void sw_mtd_kernel(const int64_t* __restr
     extern __shared__ double mtd_lds[];
     __shared__ sw_xchg X;
     sw_blk blk{&X, 0};
-    const int64_t inst = blockIdx.x;
-    const int64_t base = offsets[inst];
-    const int32_t N = (int32_t)(offsets[inst + 1] - base);
-    double* out = levels + 2 * inst;
-    if (N <= 0) { /* an empty instance (policy.flatten returns None) */
-        if (threadIdx.x == 0) { out[0] = 0.0; out[1] = 0.0; }
-        return;
-    }
-    const int32_t G = workers[inst];
-    const int32_t q = (N + SW_BLOCK - 1) / SW_BLOCK;
-    const int32_t lo = (int32_t)threadIdx.x * q;
-    const int32_t hi = lo + q < N ? lo + q : N;
-    const int32_t cnt = hi > lo ? hi - lo : 0;
+    sw_chunk ch = sw_chunk_of(offsets);
+    double* out = levels + 2 * (int64_t)blockIdx.x;
+    if (ch.N <= 0) { sw_chunk_zero<2>(out); return; }
+    ch.split();
+    const int32_t G = workers[blockIdx.x];
+    const int64_t base = ch.base;
+    const int32_t q = ch.q, lo = ch.lo, cnt = ch.cnt;
     double* xo = x + base + lo;
 
     if (q <= lds_q) {
@@ -168,96 +155,31 @@ __global__ __launch_bounds__(SW_BLOCK) void sw_mtd_kernel(const int64_t* __restr
     }
 }
 
-/* One input block and one output block per call (one copy each way):
- *   in : offsets[count+1] (int64) | p [total] (double) | sf [total],
- *        workers [count] (int32)
- *   out: x [total] | levels [count][2] (double) */
-struct MtdBufs {
-    DevBuf<unsigned char> in, out;
-    HostBuf<unsigned char> hin, hout;
-};
-
-int mtd_fail(sw_handle* h, int code, const std::string& msg) {
-    h->err = msg;
-    return code;
-}
-
-#define MTD_HIP(h, call)                                                                     \
-    do {                                                                                     \
-        hipError_t _e = (call);                                                              \
-        if (_e != hipSuccess)                                                                \
-            return mtd_fail((h), SW_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
 int mtd_run(sw_handle* h, const char* who, int32_t count, const int64_t* offsets, const int32_t* workers,
             const int32_t* sf, const double* p, double* x, double* levels) {
-    const std::string w(who);
-    if (offsets[0] != 0) return mtd_fail(h, SW_ERR_INVALID, w + ": offsets must start at 0");
-    int32_t maxq = 0;
-    for (int32_t i = 0; i < count; ++i) {
-        const int64_t n = offsets[i + 1] - offsets[i];
-        if (n < 0 || n > (int64_t)INT32_MAX - SW_BLOCK)
-            return mtd_fail(h, SW_ERR_INVALID, w + ": offsets must not decrease");
-        if (workers[i] <= 0) return mtd_fail(h, SW_ERR_INVALID, w + ": worker counts must be > 0");
-        const int32_t q = (int32_t)((n + SW_BLOCK - 1) / SW_BLOCK);
-        if (q * SW_BLOCK <= SW_MTD_LDS_JOBS && q > maxq) maxq = q;
-    }
     /* SW_MTD_LDS=0: every instance on the L2 path (A/B timing, tools/mtd_timing.py) */
-    const char* lds_env = getenv("SW_MTD_LDS");
-    if (lds_env && lds_env[0] == '0') maxq = 0;
-    const int64_t total = offsets[count];
-    if (total > 0 && (!sf || !p || !x)) return mtd_fail(h, SW_ERR_INVALID, w + ": null pointers");
-    for (int64_t j = 0; j < total; ++j) {
-        if (sf[j] < 1 || sf[j] > SW_MAX_WIDTH || !(p[j] >= 0.0) || !(p[j] <= SW_MTD_FULL_TIME_MAX))
-            return mtd_fail(h, SW_ERR_INVALID,
-                            w + ": scale factors must be in [1,255], full times finite, >= 0 and <= 1e15");
-    }
-    if (levels)
-        for (int64_t i = 0; i < 2 * (int64_t)count; ++i) levels[i] = 0.0;
-    if (total == 0) return SW_OK; /* only empty instances */
-    MTD_HIP(h, hipSetDevice(h->device));
-    if (!h->mtd) h->mtd = new MtdBufs();
-    MtdBufs* b = (MtdBufs*)h->mtd;
-    const size_t T = (size_t)total, C = (size_t)count;
-    const size_t o_p = (C + 1) * 8, o_sf = o_p + T * 8, o_w = o_sf + T * 4, in_bytes = o_w + C * 4;
-    const size_t o_lv = T * 8, out_bytes = o_lv + C * 16;
-    MTD_HIP(h, b->in.reserve(in_bytes));
-    MTD_HIP(h, b->out.reserve(out_bytes));
-    MTD_HIP(h, b->hin.reserve(in_bytes));
-    MTD_HIP(h, b->hout.reserve(out_bytes));
-    memcpy(b->hin.p, offsets, (C + 1) * 8);
-    memcpy(b->hin.p + o_p, p, T * 8);
-    memcpy(b->hin.p + o_sf, sf, T * 4);
-    memcpy(b->hin.p + o_w, workers, C * 4);
-    MTD_HIP(h, hipMemcpyAsync(b->in.p, b->hin.p, in_bytes, hipMemcpyHostToDevice, h->stream));
-    unsigned char* d = b->in.p;
-    const size_t lds = (size_t)maxq * SW_BLOCK * SW_MTD_JOB_BYTES;
-    hipLaunchKernelGGL(sw_mtd_kernel, dim3((unsigned)count), dim3(SW_BLOCK), lds, h->stream,
-                       (const int64_t*)d, (const int32_t*)(d + o_w), (const int32_t*)(d + o_sf),
-                       (const double*)(d + o_p), (double*)b->out.p, (double*)(b->out.p + o_lv), maxq);
-    MTD_HIP(h, hipGetLastError());
-    MTD_HIP(h, hipMemcpyAsync(b->hout.p, b->out.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
-    MTD_HIP(h, hipStreamSynchronize(h->stream));
-    memcpy(x, b->hout.p, T * 8);
-    if (levels) memcpy(levels, b->hout.p + o_lv, C * 16);
-    return SW_OK;
+    const sw_alloc_call call{who, count, offsets, workers, "worker counts must be > 0", 2, {{p, 8}, {sf, 4}},
+                             x, levels, 2, SW_MTD_LDS_JOBS, SW_MTD_JOB_BYTES, "SW_MTD_LDS"};
+    return sw_alloc_run(
+        h, call,
+        [=](int64_t j) -> const char* {
+            if (sf[j] < 1 || sf[j] > SW_MAX_WIDTH || !(p[j] >= 0.0) || !(p[j] <= SW_MTD_FULL_TIME_MAX))
+                return "scale factors must be in [1,255], full times finite, >= 0 and <= 1e15";
+            return nullptr;
+        },
+        [](const sw_alloc_dev& d) {
+            hipLaunchKernelGGL(sw_mtd_kernel, dim3(d.count), dim3(SW_BLOCK), d.lds, d.stream, d.offsets, d.workers,
+                               (const int32_t*)d.col[1], (const double*)d.col[0], d.x, d.levels, d.maxq);
+        });
 }
 
 }  // namespace
-
-void sw_mtd_release(sw_handle* h) {
-    if (!h || !h->mtd) return;
-    MtdBufs* b = (MtdBufs*)h->mtd;
-    b->in.release(); b->out.release(); b->hin.release(); b->hout.release();
-    delete b;
-    h->mtd = nullptr;
-}
 
 extern "C" int sw_mtd_allocate(sw_handle* h, int32_t num_jobs, int32_t num_workers,
                                const int32_t* scale_factors, const double* full_time,
                                double* allocation, double* level) {
     if (!h) return SW_ERR_INVALID;
-    if (num_jobs < 0) return mtd_fail(h, SW_ERR_INVALID, "sw_mtd_allocate: num_jobs < 0");
+    if (num_jobs < 0) return sw_fail(h, SW_ERR_INVALID, "sw_mtd_allocate: num_jobs < 0");
     const int64_t offsets[2] = {0, num_jobs};
     return mtd_run(h, "sw_mtd_allocate", 1, offsets, &num_workers, scale_factors, full_time,
                    allocation, level);
@@ -268,7 +190,7 @@ extern "C" int sw_mtd_allocate_batch(sw_handle* h, int32_t count, const int64_t*
                                      const double* full_time, double* allocation, double* levels) {
     if (!h) return SW_ERR_INVALID;
     if (count < 0 || (count > 0 && (!offsets || !num_workers)))
-        return mtd_fail(h, SW_ERR_INVALID, "sw_mtd_allocate_batch: bad count or null pointers");
+        return sw_fail(h, SW_ERR_INVALID, "sw_mtd_allocate_batch: bad count or null pointers");
     if (count == 0) return SW_OK;
     return mtd_run(h, "sw_mtd_allocate_batch", count, offsets, num_workers, scale_factors, full_time,
                    allocation, levels);

@@ -334,6 +334,18 @@ class NativeError(RuntimeError):
 _LIB = None
 
 
+# The per-job allocation policies of the allocation frame (csrc/sw_alloc.h):
+# the dtypes of the per-job columns in the order of the C arguments, their names
+# for the length error, and the number of levels per instance.
+_ALLOC = {
+    "ftf": ((np.int32, np.float64, np.float64, np.float64),
+            "scale_factors, full_time, elapsed and isolated_time", 2),
+    "wf": ((np.int32, np.float64), "scale_factors and coefficients", 2),
+    "mtd": ((np.int32, np.float64), "scale_factors and full_time", 2),
+    "mst": ((np.int32, np.float64, np.float64), "scale_factors, weights and floors", 4),
+}
+
+
 def load(path: str | None = None):
     """Load libshockwave_amd.so (raises NativeError if it is absent)."""
     global _LIB
@@ -395,24 +407,12 @@ def load(path: str | None = None):
     lib.sw_mmf_allocate.restype = C.c_int
     lib.sw_mmf_allocate_types.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip, _ip, _dp, _dp, _dp]
     lib.sw_mmf_allocate_types.restype = C.c_int
-    lib.sw_ftf_allocate.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip, _dp, _dp, _dp, _dp, _dp]
-    lib.sw_ftf_allocate.restype = C.c_int
-    lib.sw_ftf_allocate_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _ip, _ip, _dp, _dp,
-                                          _dp, _dp, _dp]
-    lib.sw_ftf_allocate_batch.restype = C.c_int
-    lib.sw_wf_allocate.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip, _dp, _dp, _dp]
-    lib.sw_wf_allocate.restype = C.c_int
-    lib.sw_wf_allocate_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _ip, _ip, _dp, _dp, _dp]
-    lib.sw_wf_allocate_batch.restype = C.c_int
-    lib.sw_mtd_allocate.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip, _dp, _dp, _dp]
-    lib.sw_mtd_allocate.restype = C.c_int
-    lib.sw_mtd_allocate_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _ip, _ip, _dp, _dp, _dp]
-    lib.sw_mtd_allocate_batch.restype = C.c_int
-    lib.sw_mst_allocate.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip, _dp, _dp, _dp, _dp]
-    lib.sw_mst_allocate.restype = C.c_int
-    lib.sw_mst_allocate_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _ip, _ip, _dp, _dp, _dp,
-                                          _dp]
-    lib.sw_mst_allocate_batch.restype = C.c_int
+    for name, (dtypes, _, _) in _ALLOC.items():
+        cols = [_ip if t is np.int32 else _dp for t in dtypes]
+        single, batch = getattr(lib, f"sw_{name}_allocate"), getattr(lib, f"sw_{name}_allocate_batch")
+        single.argtypes = [C.c_void_p, C.c_int32, C.c_int32, *cols, _dp, _dp]
+        batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _ip, *cols, _dp, _dp]
+        single.restype = batch.restype = C.c_int
     lib.sw_allox_assign.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip, _dp, _dp, _ip, _ip, _ip, _dp]
     lib.sw_allox_assign.restype = C.c_int
     lib.sw_allox_assign_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _ip, _ip, _dp, _dp, _ip, _ip,
@@ -558,27 +558,58 @@ class Solver:
                     "sw_mmf_allocate_types")
         return x, float(lvl[0]), int(lvl[1])
 
-    # ---- Gavel FinishTimeFairness allocation (include/shockwave_amd.h sw_ftf_allocate) ----
+    # ---- the per-job allocation policies (csrc/sw_alloc.h; _ALLOC above) ----
     @staticmethod
-    def _ftf_arrays(scale_factors, full_time, elapsed, isolated_time):
-        sf = np.ascontiguousarray(scale_factors, dtype=np.int32)
-        p = np.ascontiguousarray(full_time, dtype=np.float64)
-        a = np.ascontiguousarray(elapsed, dtype=np.float64)
-        e = np.ascontiguousarray(isolated_time, dtype=np.float64)
-        if not (len(sf) == len(p) == len(a) == len(e)):
-            raise ValueError("scale_factors, full_time, elapsed and isolated_time must have the same length")
-        return sf, p, a, e
+    def _alloc_columns(policy, values):
+        """The per-job columns as contiguous arrays of one length; None (an
+        absent column) stays None."""
+        dtypes, names, _ = _ALLOC[policy]
+        cols = [None if v is None else np.ascontiguousarray(v, dtype=t) for v, t in zip(values, dtypes)]
+        if any(c is not None and len(c) != len(cols[0]) for c in cols):
+            raise ValueError(f"{names} must have the same length")
+        return cols
 
+    @staticmethod
+    def _ptr(a):
+        return None if a is None else a.ctypes.data_as(_ip if a.dtype == np.int32 else _dp)
+
+    def _alloc(self, policy, values, num_workers):
+        """sw_<policy>_allocate; returns (x, levels)."""
+        cols = self._alloc_columns(policy, values)
+        x = np.zeros(len(cols[0]), dtype=np.float64)
+        lvl = np.zeros(_ALLOC[policy][2], dtype=np.float64)
+        what = f"sw_{policy}_allocate"
+        self._check(getattr(self.lib, what)(self.h, len(cols[0]), int(num_workers), *map(self._ptr, cols),
+                                            self._ptr(x), self._ptr(lvl)), what)
+        return x, lvl
+
+    def _alloc_batch(self, policy, instances, offsets):
+        """sw_<policy>_allocate_batch over (column..., num_workers) tuples;
+        returns the list of (x, levels).  A column is passed as null only when
+        every instance leaves it out; elsewhere an absent column is zeros."""
+        dtypes, _, width = _ALLOC[policy]
+        parts = [self._alloc_columns(policy, inst[:len(dtypes)]) for inst in instances]
+        count = len(parts)
+        off = np.zeros(count + 1, dtype=np.int64)
+        for i, q in enumerate(parts):
+            off[i + 1] = off[i] + len(q[0])
+        cat = [None if parts and all(q[k] is None for q in parts) else
+               np.ascontiguousarray(np.concatenate([np.zeros(len(q[0]), dtype=t) if q[k] is None else q[k]
+                                                    for q in parts]) if parts else [], dtype=t)
+               for k, t in enumerate(dtypes)]
+        g = np.ascontiguousarray([int(inst[len(dtypes)]) for inst in instances], dtype=np.int32)
+        x = np.zeros(len(cat[0]), dtype=np.float64)
+        lvl = np.zeros((count, width), dtype=np.float64)
+        coff = off if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
+        what = f"sw_{policy}_allocate_batch"
+        self._check(getattr(self.lib, what)(self.h, count, coff.ctypes.data_as(C.POINTER(C.c_int64)), self._ptr(g),
+                                            *map(self._ptr, cat), self._ptr(x), self._ptr(lvl)), what)
+        return [(x[off[i]:off[i + 1]].copy(), lvl[i]) for i in range(count)]
+
+    # ---- Gavel FinishTimeFairness allocation (include/shockwave_amd.h sw_ftf_allocate) ----
     def ftf_allocate(self, scale_factors, full_time, elapsed, isolated_time, num_workers: int):
         """x_j of the FinishTimeFairness program (one worker type); returns (x, ρ*, μ)."""
-        sf, p, a, e = self._ftf_arrays(scale_factors, full_time, elapsed, isolated_time)
-        x = np.zeros(len(sf), dtype=np.float64)
-        lvl = np.zeros(2, dtype=np.float64)
-        self._check(self.lib.sw_ftf_allocate(self.h, len(sf), int(num_workers), sf.ctypes.data_as(_ip),
-                                             p.ctypes.data_as(_dp), a.ctypes.data_as(_dp),
-                                             e.ctypes.data_as(_dp), x.ctypes.data_as(_dp),
-                                             lvl.ctypes.data_as(_dp)),
-                    "sw_ftf_allocate")
+        x, lvl = self._alloc("ftf", (scale_factors, full_time, elapsed, isolated_time), num_workers)
         return x, float(lvl[0]), float(lvl[1])
 
     def ftf_allocate_batch(self, instances, offsets=None):
@@ -586,45 +617,13 @@ class Solver:
         elapsed, isolated_time, num_workers) tuples, one kernel launch; returns
         the list of (x, ρ*, μ).  offsets (tests only) overrides the CSR offsets
         built from the instances' lengths."""
-        parts = [self._ftf_arrays(*inst[:4]) for inst in instances]
-        count = len(parts)
-        off = np.zeros(count + 1, dtype=np.int64)
-        for i, q in enumerate(parts):
-            off[i + 1] = off[i] + len(q[0])
-        cat = [np.ascontiguousarray(np.concatenate([q[k] for q in parts]) if parts else [], dtype=t)
-               for k, t in enumerate((np.int32, np.float64, np.float64, np.float64))]
-        sf, p, a, e = cat
-        g = np.ascontiguousarray([int(inst[4]) for inst in instances], dtype=np.int32)
-        x = np.zeros(len(sf), dtype=np.float64)
-        lvl = np.zeros((count, 2), dtype=np.float64)
-        coff = off if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
-        self._check(self.lib.sw_ftf_allocate_batch(self.h, count, coff.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                   g.ctypes.data_as(_ip), sf.ctypes.data_as(_ip),
-                                                   p.ctypes.data_as(_dp), a.ctypes.data_as(_dp),
-                                                   e.ctypes.data_as(_dp), x.ctypes.data_as(_dp),
-                                                   lvl.ctypes.data_as(_dp)),
-                    "sw_ftf_allocate_batch")
-        return [(x[off[i]:off[i + 1]].copy(), float(lvl[i, 0]), float(lvl[i, 1])) for i in range(count)]
+        return [(x, float(l[0]), float(l[1])) for x, l in self._alloc_batch("ftf", instances, offsets)]
 
     # ---- Gavel water-filling MaxMinFairness allocation (include/shockwave_amd.h sw_wf_allocate) ----
-    @staticmethod
-    def _wf_arrays(scale_factors, coefficients):
-        sf = np.ascontiguousarray(scale_factors, dtype=np.int32)
-        c = np.ascontiguousarray(coefficients, dtype=np.float64)
-        if len(sf) != len(c):
-            raise ValueError("scale_factors and coefficients must have the same length")
-        return sf, c
-
     def wf_allocate(self, scale_factors, coefficients, num_workers: int):
         """x_j of the water-filling MaxMinFairness allocation (one worker type);
         returns (x, L*, Σ sf_j·x_j)."""
-        sf, c = self._wf_arrays(scale_factors, coefficients)
-        x = np.zeros(len(sf), dtype=np.float64)
-        lvl = np.zeros(2, dtype=np.float64)
-        self._check(self.lib.sw_wf_allocate(self.h, len(sf), int(num_workers), sf.ctypes.data_as(_ip),
-                                            c.ctypes.data_as(_dp), x.ctypes.data_as(_dp),
-                                            lvl.ctypes.data_as(_dp)),
-                    "sw_wf_allocate")
+        x, lvl = self._alloc("wf", (scale_factors, coefficients), num_workers)
         return x, float(lvl[0]), float(lvl[1])
 
     def wf_allocate_batch(self, instances, offsets=None):
@@ -632,42 +631,12 @@ class Solver:
         num_workers) tuples, one kernel launch; returns the list of
         (x, L*, Σ sf_j·x_j).  offsets (tests only) overrides the CSR offsets
         built from the instances' lengths."""
-        parts = [self._wf_arrays(*inst[:2]) for inst in instances]
-        count = len(parts)
-        off = np.zeros(count + 1, dtype=np.int64)
-        for i, q in enumerate(parts):
-            off[i + 1] = off[i] + len(q[0])
-        sf, c = [np.ascontiguousarray(np.concatenate([q[k] for q in parts]) if parts else [], dtype=t)
-                 for k, t in enumerate((np.int32, np.float64))]
-        g = np.ascontiguousarray([int(inst[2]) for inst in instances], dtype=np.int32)
-        x = np.zeros(len(sf), dtype=np.float64)
-        lvl = np.zeros((count, 2), dtype=np.float64)
-        coff = off if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
-        self._check(self.lib.sw_wf_allocate_batch(self.h, count, coff.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                  g.ctypes.data_as(_ip), sf.ctypes.data_as(_ip),
-                                                  c.ctypes.data_as(_dp), x.ctypes.data_as(_dp),
-                                                  lvl.ctypes.data_as(_dp)),
-                    "sw_wf_allocate_batch")
-        return [(x[off[i]:off[i + 1]].copy(), float(lvl[i, 0]), float(lvl[i, 1])) for i in range(count)]
+        return [(x, float(l[0]), float(l[1])) for x, l in self._alloc_batch("wf", instances, offsets)]
 
     # ---- Gavel MinTotalDuration allocation (include/shockwave_amd.h sw_mtd_allocate) ----
-    @staticmethod
-    def _mtd_arrays(scale_factors, full_time):
-        sf = np.ascontiguousarray(scale_factors, dtype=np.int32)
-        p = np.ascontiguousarray(full_time, dtype=np.float64)
-        if len(sf) != len(p):
-            raise ValueError("scale_factors and full_time must have the same length")
-        return sf, p
-
     def mtd_allocate(self, scale_factors, full_time, num_workers: int):
         """x_j of the MinTotalDuration allocation (one worker type); returns (x, T, μ)."""
-        sf, p = self._mtd_arrays(scale_factors, full_time)
-        x = np.zeros(len(sf), dtype=np.float64)
-        lvl = np.zeros(2, dtype=np.float64)
-        self._check(self.lib.sw_mtd_allocate(self.h, len(sf), int(num_workers), sf.ctypes.data_as(_ip),
-                                             p.ctypes.data_as(_dp), x.ctypes.data_as(_dp),
-                                             lvl.ctypes.data_as(_dp)),
-                    "sw_mtd_allocate")
+        x, lvl = self._alloc("mtd", (scale_factors, full_time), num_workers)
         return x, float(lvl[0]), float(lvl[1])
 
     def mtd_allocate_batch(self, instances, offsets=None):
@@ -675,44 +644,13 @@ class Solver:
         num_workers) tuples, one kernel launch; returns the list of (x, T, μ).
         offsets (tests only) overrides the CSR offsets built from the
         instances' lengths."""
-        parts = [self._mtd_arrays(*inst[:2]) for inst in instances]
-        count = len(parts)
-        off = np.zeros(count + 1, dtype=np.int64)
-        for i, q in enumerate(parts):
-            off[i + 1] = off[i] + len(q[0])
-        sf, p = [np.ascontiguousarray(np.concatenate([q[k] for q in parts]) if parts else [], dtype=t)
-                 for k, t in enumerate((np.int32, np.float64))]
-        g = np.ascontiguousarray([int(inst[2]) for inst in instances], dtype=np.int32)
-        x = np.zeros(len(sf), dtype=np.float64)
-        lvl = np.zeros((count, 2), dtype=np.float64)
-        coff = off if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
-        self._check(self.lib.sw_mtd_allocate_batch(self.h, count, coff.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                   g.ctypes.data_as(_ip), sf.ctypes.data_as(_ip),
-                                                   p.ctypes.data_as(_dp), x.ctypes.data_as(_dp),
-                                                   lvl.ctypes.data_as(_dp)),
-                    "sw_mtd_allocate_batch")
-        return [(x[off[i]:off[i + 1]].copy(), float(lvl[i, 0]), float(lvl[i, 1])) for i in range(count)]
+        return [(x, float(l[0]), float(l[1])) for x, l in self._alloc_batch("mtd", instances, offsets)]
 
     # ---- Gavel max-sum-throughput allocation (include/shockwave_amd.h sw_mst_allocate) ----
-    @staticmethod
-    def _mst_arrays(scale_factors, weights, floors):
-        sf = np.ascontiguousarray(scale_factors, dtype=np.int32)
-        w = np.ascontiguousarray(weights, dtype=np.float64)
-        l = None if floors is None else np.ascontiguousarray(floors, dtype=np.float64)
-        if len(sf) != len(w) or (l is not None and len(l) != len(sf)):
-            raise ValueError("scale_factors, weights and floors must have the same length")
-        return sf, w, l
-
     def mst_allocate(self, scale_factors, weights, floors, num_workers: int):
         """x_j of the max-sum-throughput allocation (one worker type); floors
         may be None (all zero).  Returns (x, λ, m, objective, slo_dropped)."""
-        sf, w, l = self._mst_arrays(scale_factors, weights, floors)
-        x = np.zeros(len(sf), dtype=np.float64)
-        lvl = np.zeros(4, dtype=np.float64)
-        self._check(self.lib.sw_mst_allocate(self.h, len(sf), int(num_workers), sf.ctypes.data_as(_ip),
-                                             w.ctypes.data_as(_dp), None if l is None else l.ctypes.data_as(_dp),
-                                             x.ctypes.data_as(_dp), lvl.ctypes.data_as(_dp)),
-                    "sw_mst_allocate")
+        x, lvl = self._alloc("mst", (scale_factors, weights, floors), num_workers)
         return x, float(lvl[0]), float(lvl[1]), float(lvl[2]), bool(lvl[3])
 
     def mst_allocate_batch(self, instances, offsets=None):
@@ -721,29 +659,8 @@ class Solver:
         (x, λ, m, objective, slo_dropped).  Floors of None are zeros (the
         pointer is null when every instance has none).  offsets (tests only)
         overrides the CSR offsets built from the instances' lengths."""
-        parts = [self._mst_arrays(*inst[:3]) for inst in instances]
-        count = len(parts)
-        off = np.zeros(count + 1, dtype=np.int64)
-        for i, q in enumerate(parts):
-            off[i + 1] = off[i] + len(q[0])
-        sf, w = [np.ascontiguousarray(np.concatenate([q[k] for q in parts]) if parts else [], dtype=t)
-                 for k, t in enumerate((np.int32, np.float64))]
-        l = None
-        if any(q[2] is not None for q in parts):
-            l = np.ascontiguousarray(np.concatenate([np.zeros(len(q[0])) if q[2] is None else q[2] for q in parts]),
-                                     dtype=np.float64)
-        g = np.ascontiguousarray([int(inst[3]) for inst in instances], dtype=np.int32)
-        x = np.zeros(len(sf), dtype=np.float64)
-        lvl = np.zeros((count, 4), dtype=np.float64)
-        coff = off if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
-        self._check(self.lib.sw_mst_allocate_batch(self.h, count, coff.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                   g.ctypes.data_as(_ip), sf.ctypes.data_as(_ip),
-                                                   w.ctypes.data_as(_dp),
-                                                   None if l is None else l.ctypes.data_as(_dp),
-                                                   x.ctypes.data_as(_dp), lvl.ctypes.data_as(_dp)),
-                    "sw_mst_allocate_batch")
-        return [(x[off[i]:off[i + 1]].copy(), float(lvl[i, 0]), float(lvl[i, 1]), float(lvl[i, 2]), bool(lvl[i, 3]))
-                for i in range(count)]
+        return [(x, float(l[0]), float(l[1]), float(l[2]), bool(l[3]))
+                for x, l in self._alloc_batch("mst", instances, offsets)]
 
     # ---- AlloX assignment (include/shockwave_amd.h sw_allox_assign) ----
     @staticmethod
