@@ -349,7 +349,11 @@ int sw_mmf_allocate(sw_handle* h, int32_t num_jobs, int32_t num_workers,
  * · scale factor (the caller's normalisation, max_min_fairness.py:57-73; the
  * Fig-9 policy, MaxMinFairnessPolicy, passes unit throughputs), jobs in sorted
  * id order, types in sorted name order (policy.py:28-44).  Solved exactly by
- * the simplex method (Bland's rule) on the GPU: allocation receives an
+ * the simplex method on the GPU (csrc/sw_mmf_lp.h: the most negative
+ * objective entry enters, Bland's rule after 8 pivots without a rise of the
+ * objective; the coefficients are normalised by the power of two that brings
+ * the largest into [1, 2), so the level scales exactly with them and the
+ * allocation does not depend on their scale): allocation receives an
  * optimal vertex (row-major, unclipped), level[0] the optimal min share t*,
  * level[1] the pivots taken.  ECOS, the reference's solver, returns an
  * interior point of the same optimal face: the level is the LP's, the

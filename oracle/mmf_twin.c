@@ -57,7 +57,42 @@ int mmf_twin_allocate(int32_t N, int32_t G, const int32_t* sf, const double* c, 
 
 #include "../shockwave-replication_amd/csrc/sw_mmf_lp.h"
 
-/* The kernel's pivots, one after the other (sw_mmf.hip sw_mmf_lp_kernel).
+/* the pivot cap of an m × n problem, for the tests' bound on the pivots taken */
+int64_t mmf_twin_lp_max_pivots(int32_t m, int32_t n) {
+    const sw_lp_dims d = sw_lp_dims_of(m, n);
+    return sw_lp_max_pivots(&d);
+}
+
+/* the entering column of the objective row obj[0 … C) (k_lp_select's
+ * reduction, in column order), SW_LP_NO_COLUMN at the optimum */
+static int32_t lp_enter(const double* obj, int32_t C, int bland) {
+    int32_t e = SW_LP_NO_COLUMN;
+    double ev = 0.0;
+    for (int32_t c = 0; c < C; ++c) {
+        if (!sw_lp_enters(obj[c])) continue;
+        const double v = sw_lp_enter_key(obj[c], bland);
+        if (sw_lp_enter_before(v, c, ev, e)) { e = c; ev = v; }
+    }
+    return e;
+}
+
+/* the pieces of the pivot rule and of the normalisation, for tests/test_mmf_lp.py */
+int32_t mmf_twin_lp_enter(const double* obj, int32_t C, int32_t bland) { return lp_enter(obj, C, bland); }
+int32_t mmf_twin_lp_shift(double cmax) { return sw_lp_shift(cmax); }
+double mmf_twin_lp_scale(double v, int32_t k) { return sw_lp_scale(v, k); }
+/* feeds the objective values z[0 … n) after n pivots to the stall counter;
+ * bland[i] = whether pivot i + 1 enters by Bland's rule */
+void mmf_twin_lp_stall(const double* z, int32_t n, int32_t* bland) {
+    int64_t stall = 0;
+    double best = 0.0;
+    for (int32_t i = 0; i < n; ++i) {
+        sw_lp_note(z[i], &best, &stall);
+        bland[i] = sw_lp_bland(stall);
+    }
+}
+
+/* The kernel's pivots, one after the other (sw_mmf.hip k_lp_select and
+ * k_lp_update), by the pivot rule and the normalisation of sw_mmf_lp.h.
  * x: m·n doubles (row-major), level[0] = t*; *pivots the pivots taken.
  * Returns 0, or -2 (no leaving row: cannot happen on this bounded LP) /
  * -3 (pivot cap) / -1 (allocation). */
@@ -69,23 +104,27 @@ int mmf_twin_allocate_types(int32_t m, int32_t n, const int32_t* workers, const 
     double* f = (double*)malloc(R1 * sizeof(double));
     int32_t* basis = (int32_t*)malloc((size_t)(d.R > 0 ? d.R : 1) * sizeof(int32_t));
     if (!a || !f || !basis) { free(a); free(f); free(basis); return -1; }
+    double cmax = 0.0;
+    for (int32_t j = 0; j < m * n; ++j) cmax = coef[j] > cmax ? coef[j] : cmax;
+    const int32_t shift = sw_lp_shift(cmax);
     for (size_t i = 0; i < R1; ++i)
-        for (size_t c = 0; c < W; ++c) a[i * W + c] = sw_lp_init(&d, workers, sf, coef, (int32_t)i, (int32_t)c);
+        for (size_t c = 0; c < W; ++c)
+            a[i * W + c] = sw_lp_init(&d, workers, sf, coef, shift, (int32_t)i, (int32_t)c);
     for (int32_t i = 0; i < d.R; ++i) basis[i] = m * n + 1 + i;
     const int64_t maxp = sw_lp_max_pivots(&d);
-    int64_t piv = 0;
+    int64_t piv = 0, stall = 0;
+    double best = 0.0;
     int rc = 0;
     const double* obj = a + (size_t)d.R * W;
     for (;;) {
-        int32_t e = -1;
-        for (int32_t c = 0; c < d.C; ++c)
-            if (obj[c] < -SW_LP_EPS) { e = c; break; }
-        if (e < 0) break; /* optimal */
+        if (piv > 0) sw_lp_note(obj[d.C], &best, &stall);
+        const int32_t e = lp_enter(obj, d.C, sw_lp_bland(stall));
+        if (e == SW_LP_NO_COLUMN) break; /* optimal */
         int32_t r = -1, bb = 0;
         double rb = 0.0;
         for (int32_t i = 0; i < d.R; ++i) {
             const double v = a[(size_t)i * W + e];
-            if (v > SW_LP_EPS) {
+            if (sw_lp_leaves(v)) {
                 const double ratio = a[(size_t)i * W + d.C] / v;
                 if (r < 0 || sw_lp_before(ratio, basis[i], rb, bb)) { r = i; rb = ratio; bb = basis[i]; }
             }
@@ -111,7 +150,7 @@ int mmf_twin_allocate_types(int32_t m, int32_t n, const int32_t* workers, const 
         if (basis[i] < m * n) x[basis[i]] = v;
         else if (basis[i] == m * n) t = v;
     }
-    level[0] = t;
+    level[0] = sw_lp_scale(t, -shift);
     *pivots = piv;
     free(a); free(f); free(basis);
     return rc;

@@ -91,14 +91,21 @@ __global__ __launch_bounds__(SW_BLOCK) void sw_mmf_kernel(int32_t N, int32_t G,
  * 3 types is 3.2 MB).  A pivot is a rank-one update of the whole tableau, so
  * it runs on the whole GPU as two kernels chained on the stream, with the
  * simplex state in device memory and no host round trip per pivot:
- *   k_lp_select  (one workgroup) the entering column (first negative
- *                objective entry: a block min over column stripes), the
- *                leaving row (least ratio, then least basic index: a wave
- *                butterfly and an eight-way combine), the entering column's
- *                entries f_i and the divided pivot row p_j into buffers, the
- *                basis update; sets the done flag at the optimum;
+ *   k_lp_select  (one workgroup) the stall counter of the pivot rule
+ *                (sw_mmf_lp.h: the objective value against the best seen),
+ *                the entering column (the arg-min of (objective entry, column)
+ *                under the steep rule, of the column alone under Bland's: one
+ *                key order, a wave butterfly and an eight-way combine of
+ *                comparisons, so no reduction order can change it), the
+ *                leaving row (least ratio, then least basic index: the same
+ *                shape), the entering column's entries f_i and the divided
+ *                pivot row p_j into buffers, the basis update; sets the done
+ *                flag at the optimum;
  *   k_lp_update  (a workgroup per row) a_ij − f_i·p_j, the pivot row := p
  *                (rows with f_i = 0 are skipped).
+ * k_lp_init writes the tableau with the coefficients scaled by the power of
+ * two that brings the largest into [1, 2) (the host finds the largest while it
+ * validates them); k_lp_result scales the level back.
  * The host enqueues pivots in chunks and reads the flag between chunks.  The
  * pivots and every element's arithmetic are oracle/mmf_twin.c's, so the
  * tableau's bits are the twin's.  (A first single-workgroup form, rows
@@ -114,41 +121,76 @@ __device__ __forceinline__ void lp_take(LpKey& k, const LpKey& o) {
     if (o.i >= 0 && (k.i < 0 || sw_lp_before(o.r, o.b, k.r, k.b))) k = o;
 }
 
-/* simplex state in device memory: [0] done (0 running, 1 optimal, -2 no
- * leaving row, -3 pivot cap), [1] pivots, [2] pivot row r, [3] entering e */
+struct LpEnter {
+    double v;
+    int32_t c;
+};
+
+__device__ __forceinline__ void lp_enter_take(LpEnter& k, const LpEnter& o) {
+    if (sw_lp_enter_before(o.v, o.c, k.v, k.c)) k = o;
+}
+
+/* simplex state in device memory: done (0 running, 1 optimal, -2 no leaving
+ * row, -3 pivot cap), pivots, pivot row r, entering e, and the pivot rule's
+ * stall counter with the best objective value seen (sw_lp_note) */
 struct LpState {
-    int64_t done, piv, r, e;
+    int64_t done, piv, r, e, stall;
+    double best;
 };
 
 constexpr int kLpTB = 256;
 
-__global__ __launch_bounds__(kLpTB) void k_lp_init(int32_t m, int32_t n, const int32_t* workers, const int32_t* sf,
-                                                   const double* coef, double* a, int32_t* basis, LpState* st) {
+__global__ __launch_bounds__(kLpTB) void k_lp_init(int32_t m, int32_t n, int32_t shift, const int32_t* workers,
+                                                   const int32_t* sf, const double* coef, double* a, int32_t* basis,
+                                                   LpState* st) {
     const sw_lp_dims d = sw_lp_dims_of(m, n);
     const int64_t W = d.W, cells = ((int64_t)d.R + 1) * W;
     const int64_t g = (int64_t)blockIdx.x * kLpTB + threadIdx.x, stride = (int64_t)gridDim.x * kLpTB;
-    for (int64_t e = g; e < cells; e += stride) a[e] = sw_lp_init(&d, workers, sf, coef, (int32_t)(e / W), (int32_t)(e % W));
+    for (int64_t e = g; e < cells; e += stride)
+        a[e] = sw_lp_init(&d, workers, sf, coef, shift, (int32_t)(e / W), (int32_t)(e % W));
     for (int64_t i = g; i < d.R; i += stride) basis[i] = m * n + 1 + (int32_t)i;
-    if (g == 0) { st->done = 0; st->piv = 0; st->r = -1; st->e = -1; }
+    if (g == 0) { st->done = 0; st->piv = 0; st->r = -1; st->e = -1; st->stall = 0; st->best = 0.0; }
 }
 
 __global__ __launch_bounds__(SW_BLOCK) void k_lp_select(int32_t m, int32_t n, const double* a, int32_t* basis,
                                                         double* f, double* p, LpState* st) {
-    __shared__ sw_xchg X;
+    __shared__ LpEnter we[SW_WAVES];
     __shared__ LpKey wk[SW_WAVES];
     __shared__ int32_t sr;
     if (st->done != 0) return; /* uniform: the optimum (or a stop) was reached */
-    const int64_t piv0 = st->piv; /* read once: thread 0 advances it below */
-    sw_blk blk{&X, 0};
+    /* read once by every thread: thread 0 writes them back below, after a barrier */
+    const int64_t piv0 = st->piv;
+    int64_t stall = st->stall;
+    double best = st->best;
     const sw_lp_dims d = sw_lp_dims_of(m, n);
     const int64_t W = d.W, R1 = (int64_t)d.R + 1;
     const int tid = threadIdx.x, lane = lane_id(), wv = wave_id();
     const double* obj = a + (int64_t)d.R * W;
-    int32_t el = 0x7FFFFFFF;
-    for (int32_t c = tid; c < d.C; c += SW_BLOCK)
-        if (obj[c] < -SW_LP_EPS) { el = c; break; }
-    const int32_t e = blk.min32(el);
-    if (e == 0x7FFFFFFF) {
+    if (piv0 > 0) sw_lp_note(obj[d.C], &best, &stall); /* the pivot before this one */
+    const int bland = sw_lp_bland(stall);
+    LpEnter en;
+    en.v = 0.0; en.c = SW_LP_NO_COLUMN;
+    for (int32_t c = tid; c < d.C; c += SW_BLOCK) {
+        const double o = obj[c];
+        if (!sw_lp_enters(o)) continue;
+        LpEnter q;
+        q.v = sw_lp_enter_key(o, bland);
+        q.c = c;
+        lp_enter_take(en, q);
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        LpEnter q;
+        q.v = __shfl_xor(en.v, off, 64);
+        q.c = __shfl_xor(en.c, off, 64);
+        lp_enter_take(en, q);
+    }
+    if (lane == 0) we[wv] = en;
+    __syncthreads();
+    en = we[0];
+    for (int w = 1; w < SW_WAVES; ++w) lp_enter_take(en, we[w]);
+    const int32_t e = en.c; /* uniform: every thread combined the same eight */
+    if (e == SW_LP_NO_COLUMN) {
         if (tid == 0) st->done = 1;
         return;
     }
@@ -156,7 +198,7 @@ __global__ __launch_bounds__(SW_BLOCK) void k_lp_select(int32_t m, int32_t n, co
     k.r = 0.0; k.b = 0; k.i = -1;
     for (int32_t i = tid; i < d.R; i += SW_BLOCK) {
         const double v = a[(int64_t)i * W + e];
-        if (v > SW_LP_EPS) {
+        if (sw_lp_leaves(v)) {
             LpKey o;
             o.r = a[(int64_t)i * W + d.C] / v;
             o.b = basis[i];
@@ -191,6 +233,8 @@ __global__ __launch_bounds__(SW_BLOCK) void k_lp_select(int32_t m, int32_t n, co
     if (tid == 0) {
         basis[r] = e;
         st->piv = piv0 + 1;
+        st->stall = stall;
+        st->best = best;
         st->r = r;
         st->e = e;
     }
@@ -212,8 +256,9 @@ __global__ __launch_bounds__(kLpTB) void k_lp_update(int32_t m, int32_t n, doubl
     for (int64_t c = threadIdx.x; c < W; c += kLpTB) ai[c] = ai[c] - fi * p[c];
 }
 
-__global__ __launch_bounds__(SW_BLOCK) void k_lp_result(int32_t m, int32_t n, const double* a, const int32_t* basis,
-                                                        const LpState* st, double* x, double* out) {
+__global__ __launch_bounds__(SW_BLOCK) void k_lp_result(int32_t m, int32_t n, int32_t shift, const double* a,
+                                                        const int32_t* basis, const LpState* st, double* x,
+                                                        double* out) {
     const sw_lp_dims d = sw_lp_dims_of(m, n);
     const int64_t W = d.W;
     const int tid = threadIdx.x;
@@ -224,7 +269,7 @@ __global__ __launch_bounds__(SW_BLOCK) void k_lp_result(int32_t m, int32_t n, co
         const int32_t b = basis[i];
         const double v = a[(int64_t)i * W + d.C];
         if (b < m * n) x[b] = v;
-        else if (b == m * n) out[0] = v;
+        else if (b == m * n) out[0] = sw_lp_scale(v, -shift);
     }
     if (tid == 0) {
         out[1] = (double)st->piv;
@@ -317,6 +362,7 @@ extern "C" int sw_mmf_allocate_types(sw_handle* h, int32_t num_jobs, int32_t num
     for (int32_t k = 0; k < num_types; ++k)
         if (workers[k] < 0)
             return sw_fail(h, SW_ERR_INVALID, "sw_mmf_allocate_types: worker counts must be >= 0");
+    double cmax = 0.0;
     for (int32_t j = 0; j < num_jobs; ++j) {
         if (scale_factors[j] < 1 || scale_factors[j] > SW_MAX_WIDTH)
             return sw_fail(h, SW_ERR_INVALID, "sw_mmf_allocate_types: scale factors must be in [1,255]");
@@ -325,11 +371,13 @@ extern "C" int sw_mmf_allocate_types(sw_handle* h, int32_t num_jobs, int32_t num
             if (!(c >= 0.0) || !isfinite(c))
                 return sw_fail(h, SW_ERR_INVALID,
                                 "sw_mmf_allocate_types: coefficients must be finite and >= 0");
+            cmax = c > cmax ? c : cmax;
         }
     }
     if (level) { level[0] = 0.0; level[1] = 0.0; }
     if (num_jobs == 0) return SW_OK; /* policy.flatten returns None (policy.py:28-33) */
     const sw_lp_dims d = sw_lp_dims_of(num_jobs, num_types);
+    const int32_t shift = sw_lp_shift(cmax); /* the normalisation of sw_mmf_lp.h */
     const size_t cells = (size_t)(d.R + 1) * (size_t)d.W;
     if (cells * sizeof(double) > ((size_t)1 << 28))
         return sw_fail(h, SW_ERR_CAPACITY, "sw_mmf_allocate_types: tableau above 256 MB");
@@ -361,8 +409,8 @@ extern "C" int sw_mmf_allocate_types(sw_handle* h, int32_t num_jobs, int32_t num
     SW_HIP(h, hipMemcpyAsync(b->lsf.p, b->hlsf.p, m * 4, hipMemcpyHostToDevice, st));
     SW_HIP(h, hipMemcpyAsync(b->lc.p, b->hlc.p, mn * 8, hipMemcpyHostToDevice, st));
     const unsigned gi = (unsigned)std::min<size_t>((cells + kLpTB - 1) / kLpTB, 4096);
-    hipLaunchKernelGGL(k_lp_init, dim3(gi), dim3(kLpTB), 0, st, num_jobs, num_types, b->lw.p, b->lsf.p, b->lc.p,
-                       b->tab.p, b->lbasis.p, b->lst.p);
+    hipLaunchKernelGGL(k_lp_init, dim3(gi), dim3(kLpTB), 0, st, num_jobs, num_types, shift, b->lw.p, b->lsf.p,
+                       b->lc.p, b->tab.p, b->lbasis.p, b->lst.p);
     SW_HIP(h, hipGetLastError());
     /* pivots in chunks, the done flag read between them */
     constexpr int kChunk = 32;
@@ -379,8 +427,8 @@ extern "C" int sw_mmf_allocate_types(sw_handle* h, int32_t num_jobs, int32_t num
         SW_HIP(h, hipStreamSynchronize(st));
         if (b->hlst.p->done != 0 || done_piv > maxp) break;
     }
-    hipLaunchKernelGGL(k_lp_result, dim3(1), dim3(SW_BLOCK), 0, st, num_jobs, num_types, b->tab.p, b->lbasis.p,
-                       b->lst.p, b->lx.p, b->lout.p);
+    hipLaunchKernelGGL(k_lp_result, dim3(1), dim3(SW_BLOCK), 0, st, num_jobs, num_types, shift, b->tab.p,
+                       b->lbasis.p, b->lst.p, b->lx.p, b->lout.p);
     SW_HIP(h, hipGetLastError());
     SW_HIP(h, hipMemcpyAsync(b->hlx.p, b->lx.p, mn * 8, hipMemcpyDeviceToHost, st));
     SW_HIP(h, hipMemcpyAsync(b->hlout.p, b->lout.p, 3 * 8, hipMemcpyDeviceToHost, st));
