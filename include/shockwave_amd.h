@@ -457,6 +457,67 @@ int sw_wf_allocate_batch(sw_handle* h, int32_t count, const int64_t* offsets,
                          const double* coefficients, double* allocation, double* levels);
 
 /*
+ * The Gavel water-filling MaxMinFairness allocation with the entity hierarchy
+ * (policies/max_min_fairness_water_filling.py:21-77: priority_reweighting_policies
+ * "fairness" or "fifo" per entity) for one worker type, or several with
+ * identical throughputs.  Every job belongs to one entity (a user or a team);
+ * entity e has the weight entity_weights[e] and the mode entity_modes[e].
+ * Before each stage of its loop the reference hands an entity's weight to its
+ * unfrozen jobs: in mode 0 (fairness) in proportion to their priority weights,
+ * in mode 1 (fifo) all of it to the unfrozen job with the smallest id.  The
+ * fixed point of that process is two nested water fillings, which this call
+ * computes in one kernel.  With D_e = Σ_{j∈e} scale_factors[j]:
+ *     outer  g_e = D_e·min(1, C* / (D_e / entity_weights[e])), C* the largest
+ *            level at which Σ_e g_e ≤ num_workers;
+ *     inner  fairness: x_j = min(1, τ_e / coefficients[j]), τ_e the largest
+ *            level at which Σ_{j∈e} scale_factors[j]·x_j ≤ g_e;
+ *            fifo: the jobs of e are filled in ascending job index,
+ *            x_j = clamp((g_e − Σ_{k∈e, k<j} scale_factors[k]) /
+ *            scale_factors[j], 0, 1); their coefficients are not used.
+ * scale_factors and coefficients are those of sw_wf_allocate, in sorted
+ * job-id order; entity_of_job[j] in [0, num_entities) names job j's entity.
+ * allocation (num_jobs doubles) receives x_j; every job of an entity with
+ * g_e ≥ D_e receives exactly 1.0.  entity_capacity (optional, num_entities
+ * doubles) receives g_e; an entity without jobs is allowed and receives 0.
+ * level (optional, 2 doubles) receives C* and the allocated capacity
+ * Σ_j scale_factors[j]·x_j (the kernel's deterministic sum).  When
+ * Σ_j scale_factors[j] ≤ num_workers every x_j is 1 and C* is the largest
+ * D_e / entity_weights[e] over the entities that have jobs.
+ * SW_ERR_INVALID: the per-job cases of sw_wf_allocate; an entity_of_job
+ * outside [0, num_entities); an entity weight that is not finite and > 0; a
+ * mode other than 0 or 1; num_workers ≤ 0; null pointers with num_jobs > 0;
+ * num_jobs < 0 or num_entities < 0.  Synchronous; num_jobs = 0 is a no-op that
+ * returns SW_OK with the level (0, 0) and every entity capacity 0.
+ */
+int sw_wfh_allocate(sw_handle* h, int32_t num_jobs, int32_t num_entities, int32_t num_workers,
+                    const int32_t* scale_factors, const double* coefficients,
+                    const int32_t* entity_of_job, const double* entity_weights,
+                    const int32_t* entity_modes, double* allocation, double* entity_capacity,
+                    double* level);
+
+/*
+ * count independent instances of sw_wfh_allocate in one kernel launch.
+ * Instance i owns the jobs [job_offsets[i], job_offsets[i+1]) of the per-job
+ * arrays, the entities [entity_offsets[i], entity_offsets[i+1]) of the
+ * per-entity arrays (two CSR arrays of count + 1 entries) and num_workers[i]
+ * workers; entity_of_job counts from the instance's first entity.
+ * entity_capacity (optional) covers every entity, levels (optional) is
+ * [count][2].  Every instance's result is bit for bit that of the single
+ * call; an empty instance is allowed and yields the level (0, 0).
+ * SW_ERR_INVALID: offsets of either kind that do not start at 0 or that
+ * decrease; any num_workers[i] ≤ 0; the cases of sw_wfh_allocate; count < 0;
+ * null offsets or num_workers with count > 0; null per-job pointers with jobs
+ * present, null per-entity pointers with entities present.  Synchronous;
+ * count = 0 is a no-op that returns SW_OK.
+ */
+int sw_wfh_allocate_batch(sw_handle* h, int32_t count, const int64_t* job_offsets,
+                          const int64_t* entity_offsets, const int32_t* num_workers,
+                          const int32_t* scale_factors, const double* coefficients,
+                          const int32_t* entity_of_job, const double* entity_weights,
+                          const int32_t* entity_modes, double* allocation,
+                          double* entity_capacity, double* levels);
+
+/*
  * The Gavel MinTotalDuration (makespan) baseline's allocation
  * (policies/min_total_duration.py:41-106, selected as min_total_duration in
  * utils.get_policy) for one worker type, or several with identical

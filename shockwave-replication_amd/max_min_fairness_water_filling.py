@@ -23,10 +23,12 @@ normalised effective throughputs and the job ids (:550-551): Σ_k x[j][k] for
 the WithPerf policy.  The result is clipped to [0, 1] (:556).  A native error
 raises; there is no CPU fallback.
 
-Not built:
+Not built here:
   * the entity hierarchy (``priority_reweighting_policies`` "fairness" and
-    "fifo", :21-77): a constructor argument other than None raises
-    ``NotImplementedError``; ``entity_weights`` and ``entity_to_job_mapping``
+    "fifo", :21-77) is built by the classes of
+    ``max_min_fairness_water_filling_hierarchical``; in these two classes a
+    constructor argument other than None still raises ``NotImplementedError``
+    (naming those classes); ``entity_weights`` and ``entity_to_job_mapping``
     are accepted and, as in the reference without reweighting (:30-32), unused.
     The reference scheduler never passes entities (scheduler.py:2433-2436);
   * throughputs that differ by worker type: ``NotImplementedError`` (the staged
@@ -66,7 +68,9 @@ def _proportional_throughputs(throughputs, worker_types, cluster_spec):
 def _check_reweighting(priority_reweighting_policies):
     if priority_reweighting_policies is not None:
         raise NotImplementedError(
-            "the entity hierarchy (priority_reweighting_policies 'fairness' / 'fifo') is not built")
+            "the entity hierarchy (priority_reweighting_policies 'fairness' / 'fifo') is built by "
+            "MaxMinFairnessWaterFillingHierarchicalPolicy and ...PolicyWithPerf in "
+            "max_min_fairness_water_filling_hierarchical, not by this class")
 
 
 class MaxMinFairnessWaterFillingPolicyWithPerf:

@@ -320,6 +320,7 @@ EXPORTED_SYMBOLS = (
     "sw_mmf_allocate_types", "sw_batch_keep_masks", "sw_ftf_allocate", "sw_ftf_allocate_batch",
     "sw_wf_allocate", "sw_wf_allocate_batch", "sw_mtd_allocate", "sw_mtd_allocate_batch",
     "sw_mst_allocate", "sw_mst_allocate_batch", "sw_allox_assign", "sw_allox_assign_batch",
+    "sw_wfh_allocate", "sw_wfh_allocate_batch",
 )
 
 
@@ -418,6 +419,11 @@ def load(path: str | None = None):
     lib.sw_allox_assign_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _ip, _ip, _dp, _dp, _ip, _ip,
                                           _ip, C.POINTER(C.c_int64), _dp]
     lib.sw_allox_assign_batch.restype = C.c_int
+    lib.sw_wfh_allocate.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _ip, _dp, _ip, _dp, _ip, _dp, _dp, _dp]
+    lib.sw_wfh_allocate.restype = C.c_int
+    lib.sw_wfh_allocate_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _ip,
+                                          _ip, _dp, _ip, _dp, _ip, _dp, _dp, _dp]
+    lib.sw_wfh_allocate_batch.restype = C.c_int
     if path is None:
         _LIB = lib
     return lib
@@ -632,6 +638,59 @@ class Solver:
         (x, L*, Σ sf_j·x_j).  offsets (tests only) overrides the CSR offsets
         built from the instances' lengths."""
         return [(x, float(l[0]), float(l[1])) for x, l in self._alloc_batch("wf", instances, offsets)]
+
+    # ---- hierarchical (entity) water filling (include/shockwave_amd.h sw_wfh_allocate) ----
+    @staticmethod
+    def _wfh_arrays(scale_factors, coefficients, entity_of_job, entity_weights, entity_modes):
+        sf = np.ascontiguousarray(scale_factors, dtype=np.int32)
+        c = np.ascontiguousarray(coefficients, dtype=np.float64)
+        ent = np.ascontiguousarray(entity_of_job, dtype=np.int32)
+        w = np.ascontiguousarray(entity_weights, dtype=np.float64)
+        modes = np.ascontiguousarray(entity_modes, dtype=np.int32)
+        if not (len(sf) == len(c) == len(ent)):
+            raise ValueError("scale_factors, coefficients and entity_of_job must have the same length")
+        if len(w) != len(modes):
+            raise ValueError("entity_weights and entity_modes must have the same length")
+        return sf, c, ent, w, modes
+
+    def wfh_allocate(self, scale_factors, coefficients, entity_of_job, entity_weights, entity_modes,
+                     num_workers: int):
+        """x_j of the hierarchical water-filling allocation (one worker type;
+        entity_modes 0 fairness, 1 fifo); returns (x, g_e, C*, Σ sf_j·x_j)."""
+        sf, c, ent, w, modes = self._wfh_arrays(scale_factors, coefficients, entity_of_job, entity_weights,
+                                                entity_modes)
+        x = np.zeros(len(sf), dtype=np.float64)
+        g = np.zeros(len(w), dtype=np.float64)
+        lvl = np.zeros(2, dtype=np.float64)
+        self._check(self.lib.sw_wfh_allocate(self.h, len(sf), len(w), int(num_workers),
+                                             *map(self._ptr, (sf, c, ent, w, modes, x, g, lvl))), "sw_wfh_allocate")
+        return x, g, float(lvl[0]), float(lvl[1])
+
+    def wfh_allocate_batch(self, instances, job_offsets=None, entity_offsets=None):
+        """sw_wfh_allocate_batch over a list of (scale_factors, coefficients,
+        entity_of_job, entity_weights, entity_modes, num_workers) tuples, one
+        kernel launch; returns the list of (x, g_e, C*, Σ sf_j·x_j).  The
+        offsets (tests only) override the CSR offsets built from the
+        instances' lengths."""
+        parts = [self._wfh_arrays(*inst[:5]) for inst in instances]
+        count = len(parts)
+        off, eoff = np.zeros(count + 1, dtype=np.int64), np.zeros(count + 1, dtype=np.int64)
+        for i, q in enumerate(parts):
+            off[i + 1], eoff[i + 1] = off[i] + len(q[0]), eoff[i] + len(q[3])
+        dtypes = (np.int32, np.float64, np.int32, np.float64, np.int32)
+        cat = [np.ascontiguousarray(np.concatenate([q[k] for q in parts]) if parts else [], dtype=t)
+               for k, t in enumerate(dtypes)]
+        gw = np.ascontiguousarray([int(inst[5]) for inst in instances], dtype=np.int32)
+        x = np.zeros(len(cat[0]), dtype=np.float64)
+        g = np.zeros(len(cat[3]), dtype=np.float64)
+        lvl = np.zeros((count, 2), dtype=np.float64)
+        coff = off if job_offsets is None else np.ascontiguousarray(job_offsets, dtype=np.int64)
+        ceoff = eoff if entity_offsets is None else np.ascontiguousarray(entity_offsets, dtype=np.int64)
+        lp = C.POINTER(C.c_int64)
+        self._check(self.lib.sw_wfh_allocate_batch(self.h, count, coff.ctypes.data_as(lp), ceoff.ctypes.data_as(lp),
+                                                   *map(self._ptr, (gw, *cat, x, g, lvl))), "sw_wfh_allocate_batch")
+        return [(x[off[i]:off[i + 1]].copy(), g[eoff[i]:eoff[i + 1]].copy(), float(lvl[i, 0]), float(lvl[i, 1]))
+                for i in range(count)]
 
     # ---- Gavel MinTotalDuration allocation (include/shockwave_amd.h sw_mtd_allocate) ----
     def mtd_allocate(self, scale_factors, full_time, num_workers: int):
