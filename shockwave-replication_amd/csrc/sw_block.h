@@ -138,6 +138,13 @@ __device__ __forceinline__ uint64_t wave_min_u64(uint64_t x) {
 #undef SW_MINU_
     return sw_readlane63_u64(x);
 }
+/* bitwise OR over the wave (uniform result) */
+__device__ __forceinline__ uint64_t wave_or_u64(uint64_t x) {
+#define SW_ORU_(c, rm) x |= SW_DPP64(x, 0ull, c, rm);
+    SW_DPP64_STEPS(SW_ORU_)
+#undef SW_ORU_
+    return sw_readlane63_u64(x);
+}
 /* max of doubles (identity −inf) */
 __device__ __forceinline__ double wave_max_f64(double v) {
     uint64_t x = __builtin_bit_cast(uint64_t, v);

@@ -2108,8 +2108,21 @@ __device__ __forceinline__ const uint64_t* pack_instance(const sw_batch_dev& B, 
             if (threadIdx.x == 0) out->status = SW_STATUS_SLOW_MARK;
             return nullptr;
         }
-        /* twin_plan_solve's first pack: the density order (mode 4) */
-        c.pack(4, c.nbest, c.ycur, c.placed);
+        /* twin_plan_solve's first pack: the density order (mode 4) — pack()'s
+         * three parts, with position t's job left in the loop workspace for
+         * the exchange step's rank order (pack_tail), as sw_sort_kernel
+         * leaves it */
+        __syncthreads();
+        uint64_t khi[SW_JPT], klo[SW_JPT];
+        int A_, jp1 = 0;
+        bool mine = false;
+        uint32_t st1 = 0u;
+        c.pack_front(4, c.nbest, c.ycur, khi, klo, A_, mine, jp1, st1); /* one position per thread: A_ ≤ SW_BLOCK */
+        if (mine) B.lws[jo + threadIdx.x] = st1 | ((uint32_t)jp1 << 16);
+        if (threadIdx.x == 0) B.lwa[inst_] = A_;
+        uint64_t mk1 = 0ull;
+        c.pack_loop(4, A_, st1, mk1);
+        c.pack_back(4, c.nbest, c.ycur, c.placed, mine, jp1, st1, mk1);
     } else {
         /* the same pack, its front half and loop already run: position t's
          * word and round mask from the workspace into pack()'s back half
@@ -2179,6 +2192,13 @@ __device__ __forceinline__ const uint64_t* pack_instance(const sw_batch_dev& B, 
  * sw_p2x_instance (sw_p2x_inst.h), so the same masks and P2 bits; it only
  * moves where the arrays live and drops the mask round trip through HBM
  * (written back from L2 for every instance of the batch).
+ *
+ * The density pack's positions are in the loop workspace (B.lws, B.lwa:
+ * sw_sort_kernel's, the jobs kept by sw_rounds_kernel; pack_instance's own in
+ * the fused kernel), and the step takes its rank order from them when they
+ * prove to be it (sw_p2x_rank.h) — read again from the workspace here rather
+ * than kept live across the pack.  The placed jobs are the positions' jobs,
+ * repaired or not: the counts are the same.
  */
 __device__ __forceinline__ void pack_tail(const sw_batch_dev& B, const uint64_t* ym, unsigned char* smem,
                                           int inst) {
@@ -2233,7 +2253,12 @@ __device__ __forceinline__ void pack_tail(const sw_batch_dev& B, const uint64_t*
 #else
         uint64_t* sp = nullptr;
 #endif
-        const int nc = sw_p2x_block<SW_WAVES>(blk, L, var, X, A, T, G, sp);
+        sw_p2x_cand cand;
+        cand.pos = B.lws + jo;
+        cand.n = sw_u32(B.lwa[inst]);
+        cand.njobs = N;
+        const int nc = sw_p2x_block<SW_WAVES>(blk, L, var, X, A, T, G, sp, nullptr, nullptr,
+                                              &cand);
         __syncthreads(); /* the cancels' mask updates */
         /* the final masks: this thread's active jobs (count > 0, unchanged by
          * the step: B.planned) in compaction order, the offsets counted again

@@ -5,7 +5,9 @@
  * sharded engine on its gathered placement (sw_shard.hip).
  *
  * Mapping.  Active jobs are ranked inside their width class by (c desc, job
- * asc) with a bitonic sort (shuffles below stride 64, LDS above), and each
+ * asc) with a bitonic sort (shuffles below stride 64, LDS above) — or, when
+ * the caller hands in the density pack's positions and they prove to be that
+ * order, by a stable partition by class alone (sw_p2x_rank.h) — and each
  * class's membership of each round becomes a rank bitset in LDS (one wave
  * ballot per 64-rank word), so the move an edge t → u makes is a few 64-bit
  * and-not / ctz / clz word operations.  Edge costs W[t][u] are built by all
@@ -27,6 +29,7 @@
 #include "sw_block.h"
 #include "sw_device.h"
 #include "sw_p2x.h"
+#include "sw_p2x_rank.h"
 
 /* per-active-job arrays, index a = active jobs in job order (LDS on the
  * on-chip batch path, HBM workspace otherwise) */
@@ -58,6 +61,15 @@ struct sw_p2x_pre {
 enum { SW_P2X_HDR_K = 0, SW_P2X_HDR_WC = 1, SW_P2X_HDR_M = 9, SW_P2X_HDR_OFF = 17,
        SW_P2X_HDR_NW = 26, SW_P2X_HDR_BOFF = 34, SW_P2X_HDR_A = 42, SW_P2X_HDR_INTS = 48 };
 
+/* A candidate for the rank order (sw_p2x_rank.h): the active jobs as n
+ * positions, position q's job in the bits above 16 of pos[q] (the pack's
+ * position word, sw_kernels.hip), every job below njobs.  The set-up takes the
+ * order from it when it proves to be the rank order, and sorts otherwise. */
+struct sw_p2x_cand {
+    const uint32_t* pos;
+    int32_t n, njobs;
+};
+
 /* fixed LDS part */
 struct sw_p2x_lds {
     sw_xchg X;
@@ -65,7 +77,6 @@ struct sw_p2x_lds {
         boff[SW_P2X_KMAX];
     int32_t K, len, nrec, pad;
     uint64_t touched; /* rounds the last cancelled cycle moved jobs in or out of */
-    uint32_t wmap[8]; /* widths present (256 bits) */
     int32_t room[SW_TMAX];
     int32_t pr[SW_TMAX + 1];
     int32_t cyc[SW_TMAX + 2];
@@ -537,6 +548,7 @@ struct sw_p2x_state {
     double* W;    /* [T][T] edge costs, δ included  */
     int8_t* Wk;   /* [T][T] the edge's class        */
     double delta;
+    int ranked;   /* the positions came from the candidate (no sort) */
 };
 
 /* L->fq for load size F: F / w_k for the classes that can carry F, 0 for the
@@ -547,6 +559,156 @@ static __device__ __forceinline__ void p2x_load_size(sw_p2x_lds* L, int K, int F
         const int wk = tid < K ? L->wc[tid] : 0;
         L->fq[tid] = (wk > 0 && wk <= F && F % wk == 0 && F / wk <= SW_P2X_QMAX) ? F / wk : 0;
     }
+}
+
+/* The width classes of the A active jobs, ascending, with their sizes and
+ * offsets (L->K, wc, M, off, nw, boff; K = −1 for more than SW_P2X_KMAX).
+ * Each wave peels its jobs' widths one at a time — the first remaining
+ * lane's width, a ballot of the lanes that share it, a popcount — into a list
+ * of at most SW_P2X_KMAX (width, count) pairs, one per lane; wave 0 merges the
+ * waves' lists by peeling their smallest width, so the classes come out
+ * ascending, and scans the sizes.  No atomics and no serial loop.  The lists
+ * go through L->pv, which is dead outside Bellman–Ford.  Ends with a barrier. */
+template <int NW>
+static __device__ __forceinline__ void p2x_classes(sw_p2x_lds* L, const int32_t* cw, int A, int T) {
+    constexpr int NT = NW * 64, KM = SW_P2X_KMAX, NONE = 0x7FFFFFFF;
+    static_assert(NW * KM <= 64 && (2 * NW * KM + NW) * 4 <= (int)sizeof(L->pv),
+                  "one lane of wave 0 per list entry; the lists fit L->pv");
+    const int lane = lane_id(), wv = wave_id();
+    int32_t* wl = reinterpret_cast<int32_t*>(&L->pv[0][0]); /* [NW][KM] widths */
+    int32_t* cl = wl + NW * KM;                             /* [NW][KM] counts */
+    int32_t* ov = cl + NW * KM;                             /* [NW] more than KM widths in the wave */
+    int lw = NONE, lc = 0, nl = 0;
+    bool over = false;
+    for (int a0 = wv * 64; a0 < A && !over; a0 += NT) {
+        const int a = a0 + lane;
+        const int w = a < A ? cw[a] : 0;
+        uint64_t rem = __ballot(a < A);
+        while (rem) {
+            const int w0 = __builtin_amdgcn_readlane(w, (int)__builtin_ctzll(rem));
+            const uint64_t same = __ballot(w == w0) & rem;
+            rem &= ~same;
+            if (__ballot(lw == w0) != 0) {
+                lc += lw == w0 ? __popcll(same) : 0;
+            } else if (nl < KM) {
+                if (lane == nl) {
+                    lw = w0;
+                    lc = __popcll(same);
+                }
+                ++nl;
+            } else {
+                over = true;
+                rem = 0;
+            }
+        }
+    }
+    if (lane < KM) {
+        wl[wv * KM + lane] = lw;
+        cl[wv * KM + lane] = lc;
+    }
+    if (lane == 0) ov[wv] = over ? 1 : 0;
+    __syncthreads();
+    if (wv == 0) {
+        int w = lane < NW * KM ? wl[lane] : NONE;
+        const int c = lane < NW * KM ? cl[lane] : 0;
+        int K = __ballot(lane < NW && ov[lane] != 0) != 0 ? KM + 1 : 0;
+        int myw = 0, myM = 0;
+        while (K <= KM) {
+            const int wmin = wave_min_i32(w);
+            if (wmin == NONE) break;
+            const bool s = w == wmin;
+            const int m = wave_sum_i32(s ? c : 0);
+            if (lane == K) {
+                myw = wmin;
+                myM = m;
+            }
+            w = s ? NONE : w;
+            ++K;
+        }
+        if (K > KM) {
+            if (lane == 0) L->K = -1;
+        } else {
+            const int nwk = (myM + 63) / 64; /* 0 in the lanes past K */
+            const int incM = wave_incscan_i32(myM), incB = wave_incscan_i32(nwk * T);
+            if (lane < K) {
+                L->wc[lane] = myw;
+                L->M[lane] = myM;
+                L->nw[lane] = nwk;
+                L->boff[lane] = incB - nwk * T;
+            }
+            if (lane <= K) L->off[lane] = incM - myM;
+            if (lane == 0) L->K = K;
+        }
+    }
+    __syncthreads();
+}
+
+/* The positions from a candidate order (sw_p2x_rank.h) when A ≤ NT: thread q
+ * finds its position's active index through a 16-bit job → a table, its class
+ * and its rank among the earlier positions of the class (a ballot per class,
+ * the waves' counts combined through L->pv), stages (ckey, job) at its
+ * destination in the rank sort's scratch xs (room bytes, dead until the
+ * bitsets), and checks its predecessor there; a block-wide AND decides.  True:
+ * ord and pc are written, as the sort would have.  False: nothing is, and
+ * the caller sorts.  Uniform; ends with a barrier. */
+template <int NW>
+static __device__ __forceinline__ bool p2x_rank_from(sw_blk_t<NW>& blk, sw_p2x_lds* L, unsigned char* xs,
+                                                     size_t room, const sw_p2x_arrays& X, int A, int K,
+                                                     const sw_p2x_cand& cand, int32_t* ord, double* pc) {
+    constexpr int KM = SW_P2X_KMAX;
+    const int tid = threadIdx.x, lane = lane_id(), wv = wave_id();
+    const int nj = cand.njobs;
+    if (cand.n != A || nj <= 0 || sw_p2x_rank_bytes(A, nj) > room) return false;
+    uint64_t* skey = reinterpret_cast<uint64_t*>(xs);
+    int32_t* sjob = reinterpret_cast<int32_t*>(xs + (((size_t)A * 8 + 15) & ~(size_t)15));
+    uint16_t* j2a = reinterpret_cast<uint16_t*>(reinterpret_cast<unsigned char*>(sjob) +
+                                                (((size_t)A * 4 + 15) & ~(size_t)15));
+    int32_t* cnt = reinterpret_cast<int32_t*>(&L->pv[0][0]); /* [NW][KM]: dead outside Bellman–Ford */
+    const bool mine = tid < A;
+    const int job = mine ? (int)(cand.pos[tid] >> 16) : 0;
+    if (mine) {
+        const int j = X.cj[tid];
+        if ((unsigned)j < (unsigned)nj) j2a[j] = (uint16_t)tid;
+    }
+    __syncthreads();
+    /* the table has entries for the active jobs only: an entry is this job's
+     * when the active index it names holds the job */
+    bool ok = true;
+    int a = 0, k = 0;
+    if (mine) {
+        ok = job < nj;
+        a = ok ? (int)j2a[job] : 0;
+        ok = ok && a < A;
+        a = ok ? a : 0;
+        ok = ok && X.cj[a] == job;
+        k = p2x_class(L, X.cw[a]);
+    }
+    int r = 0;
+    for (int kk = 0; kk < K; ++kk) {
+        const uint64_t same = __ballot(mine && k == kk);
+        r = k == kk ? sw_p2x_rank_lane(same, lane) : r;
+        if (lane == 0) cnt[wv * KM + kk] = __popcll(same);
+    }
+    __syncthreads();
+    for (int w = 0; w < wv; ++w) r += cnt[w * KM + k];
+    const int dst = mine ? sw_p2x_rank_dst(L->off, k, r) : 0;
+    ok = ok && dst >= 0;
+    const double c = X.cc[a];
+    if (mine && ok) {
+        skey[dst] = sw_p2x_ckey(c);
+        sjob[dst] = job;
+    }
+    __syncthreads();
+    if (mine && ok) ok = sw_p2x_rank_ok(skey, sjob, L->off, k, dst) != 0;
+    const bool all = blk.min32(ok ? 1 : 0) != 0;
+    if (all) {
+        if (mine) {
+            ord[dst] = a;
+            pc[dst] = c;
+        }
+        __syncthreads(); /* the staging is read before the bitsets overwrite it */
+    }
+    return all;
 }
 
 /* EMAX: entries per thread the rank sort may hold in registers (the sharded
@@ -560,7 +722,7 @@ template <int NW, int EMAX = 1, bool SETUP_ONLY = false>
 __device__ __forceinline__ int sw_p2x_block(sw_blk_t<NW>& blk, sw_p2x_lds* L, unsigned char* var,
                                             const sw_p2x_arrays& X, int A, int T, int G,
                                             uint64_t* sp = nullptr, const sw_p2x_pre* pre = nullptr,
-                                            sw_p2x_state* st = nullptr) {
+                                            sw_p2x_state* st = nullptr, const sw_p2x_cand* cand = nullptr) {
     constexpr int NT = NW * 64;
     const int tid = threadIdx.x;
     (void)sp;
@@ -583,39 +745,8 @@ __device__ __forceinline__ int sw_p2x_block(sw_blk_t<NW>& blk, sw_p2x_lds* L, un
     }
     if (!pre) {
     /* ---- width classes (ascending) ---- */
-    if (tid < 8) L->wmap[tid] = 0u;
-    __syncthreads();
-    for (int a = tid; a < A; a += NT) atomicOr(&L->wmap[X.cw[a] >> 5], 1u << (X.cw[a] & 31));
-    __syncthreads();
-    if (tid == 0) {
-        int K = 0;
-        for (int i = 0; i < 8; ++i) K += __builtin_popcount(L->wmap[i]);
-        if (K > SW_P2X_KMAX) {
-            L->K = -1;
-        } else {
-            K = 0;
-            for (int i = 0; i < 8; ++i)
-                for (uint32_t b = L->wmap[i]; b; b &= b - 1) L->wc[K++] = 32 * i + __builtin_ctz(b);
-            L->K = K;
-            for (int k = 0; k < K; ++k) L->M[k] = 0;
-        }
-    }
-    __syncthreads();
+    p2x_classes<NW>(L, X.cw, A, T);
     if (L->K < 0) return 0;
-    for (int a = tid; a < A; a += NT) atomicAdd(&L->M[p2x_class(L, X.cw[a])], 1);
-    __syncthreads();
-    if (tid == 0) {
-        const int K = L->K;
-        int o = 0, b = 0;
-        for (int k = 0; k < K; ++k) {
-            L->off[k] = o;
-            L->nw[k] = (L->M[k] + 63) / 64;
-            L->boff[k] = b;
-            o += L->M[k];
-            b += L->nw[k] * T;
-        }
-        L->off[K] = o;
-    }
     } /* !pre */
     const int K = L->K;
     P2X_STAMP(0);
@@ -623,12 +754,12 @@ __device__ __forceinline__ int sw_p2x_block(sw_blk_t<NW>& blk, sw_p2x_lds* L, un
     double* pc = reinterpret_cast<double*>(var);                      /* c by position        */
     int32_t* ord = reinterpret_cast<int32_t*>(var + (size_t)A * 8);  /* position → a         */
     unsigned char* vb = var + (size_t)A * 8 + (((size_t)A * 4 + 15) & ~(size_t)15);
-    __syncthreads();
     const int nwords = L->boff[K - 1] + L->nw[K - 1] * T;
     uint64_t* B = reinterpret_cast<uint64_t*>(vb);
     double* W = reinterpret_cast<double*>(vb + (size_t)nwords * 8);
     int8_t* Wk = reinterpret_cast<int8_t*>(W + T * T);
     int32_t* rec = reinterpret_cast<int32_t*>(reinterpret_cast<unsigned char*>(Wk) + ((T * T + 15) & ~15));
+    bool ranked = false;
     /* ---- positions: (class asc, sw_p2x_ckey(c) desc, job asc) by a bitonic
      *      sort in LDS over the next power of two (the bitset / W area is
      *      free until the first build) ---- */
@@ -639,6 +770,10 @@ __device__ __forceinline__ int sw_p2x_block(sw_blk_t<NW>& blk, sw_p2x_lds* L, un
         }
         for (int i = tid; i < nwords; i += NT) B[i] = pre->B[i];
         __syncthreads();
+    } else if (A <= NT && cand &&
+               p2x_rank_from<NW>(blk, L, vb, sw_p2x_var_bytes(A, T) - (size_t)(vb - var), X, A, K, *cand, ord,
+                                 pc)) {
+        ranked = true; /* the candidate was the rank order */
     } else if (A <= NT) {
         /* one position per thread: (class, key) and (job << 32 | a), a
          * bitonic network over the next power of two np with shuffles for
@@ -807,9 +942,7 @@ __device__ __forceinline__ int sw_p2x_block(sw_blk_t<NW>& blk, sw_p2x_lds* L, un
         static_assert(NT == SW_DET_LANES, "one thread per deterministic-sum lane");
         double acc = 0.0;
         for (int p = tid * q; p < A && p < (tid + 1) * q; ++p) {
-            int64_t S = 0;
-            for (uint64_t x = X.cm[ord[p]]; x; x &= x - 1) S += __builtin_ctzll(x);
-            acc = acc + pc[p] * (double)S;
+            acc = acc + pc[p] * (double)sw_mask_tsum(X.cm[ord[p]]); /* Σ_t t·bit_t, the same integer */
         }
         const double P0 = blk.detsum(acc); /* its barrier publishes B, room */
         if (tid == 0) L->delta = sw_p2x_delta(P0, T, A);
@@ -825,6 +958,7 @@ __device__ __forceinline__ int sw_p2x_block(sw_blk_t<NW>& blk, sw_p2x_lds* L, un
         st->W = W;
         st->Wk = Wk;
         st->delta = delta;
+        st->ranked = ranked ? 1 : 0;
         return 1;
     }
     /* ---- cancelling ---- */
@@ -882,7 +1016,7 @@ __device__ __forceinline__ int sw_p2x_block(sw_blk_t<NW>& blk, sw_p2x_lds* L, un
                         const int i = b0 + lane;
                         const int u = i < len ? L->cyc[i] : T, t = i < len ? L->cyc[(i + 1) % len] : T;
                         const bool real = u < T && t < T;
-                        const int q = real ? F / L->wc[Wk[t * T + u]] : 0;
+                        const int q = real ? L->fq[Wk[t * T + u]] : 0; /* F / w_k: the edge's class carries F */
                         moves += wave_sum_i32(q);
                     }
                     int n0 = 0;
@@ -891,7 +1025,7 @@ __device__ __forceinline__ int sw_p2x_block(sw_blk_t<NW>& blk, sw_p2x_lds* L, un
                         const int u = i < len ? L->cyc[i] : T, t = i < len ? L->cyc[(i + 1) % len] : T;
                         const bool real = u < T && t < T;
                         const int k = real ? Wk[t * T + u] : 0;
-                        const int q = real ? F / L->wc[k] : 0;
+                        const int q = real ? L->fq[k] : 0;
                         const int incl = wave_incscan_i32(q);
                         if (real) tm |= (1ull << t) | (1ull << u);
                         if (real && moves <= SW_P2X_MAX_MOVES) {
@@ -907,10 +1041,7 @@ __device__ __forceinline__ int sw_p2x_block(sw_blk_t<NW>& blk, sw_p2x_lds* L, un
                         n0 += __shfl(incl, 63, 64);
                     }
                     /* every lane's touched rounds */
-                    for (int o = 32; o >= 1; o >>= 1) {
-                        const uint64_t v = (uint64_t)__shfl_xor((long long)tm, o, 64);
-                        tm |= v;
-                    }
+                    tm = wave_or_u64(tm);
                     if (lane == 0) {
                         L->nrec = moves <= SW_P2X_MAX_MOVES ? n0 : -1;
                         L->touched = tm;
