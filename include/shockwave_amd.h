@@ -247,6 +247,21 @@ int sw_kernel_times(sw_handle* h, double* ms_p2x, double* ms_plan, int32_t* runs
  *   - at every world the result equals the CPU shard engine
  *     (oracle/shard_twin.c) bit for bit.
  *
+ * Job limits (each a clean SW_ERR_CAPACITY with a message; the handle stays
+ * usable).  With M = 512·⌈total_jobs/512⌉:
+ *   - total_jobs ≤ 131,072 (256 jobs per lane of the deterministic sum);
+ *   - one share holds at most 32,768 entries when a rank has one share
+ *     (M/world of them: world 1 without eight shares ends at 32,768 jobs,
+ *     world 2 at 65,536) and at most 10,240 when it has several (always met:
+ *     eight shares of 65,536 jobs are 8,192 each);
+ *   - a gathered placement — taken when a share placement and its repair
+ *     leave rounds unplaced, by the orders after it, the raises and the P2
+ *     attempts — holds at most M = 32,768 entries at every world.  So an
+ *     instance of 32,769 … 65,536 jobs on at least 512 GPUs (eight shares)
+ *     solves as long as its shares place every round, repairs included, as
+ *     trace-shaped instances do; otherwise the solve is refused ("sharded
+ *     placement holds at most 32768 jobs") where the CPU shard engine goes on.
+ *
  * unique_id points to SW_NCCL_UNIQUE_ID_BYTES bytes produced by
  * sw_dist_unique_id() on rank 0 and broadcast by the caller.  local describes
  * this rank's slice of jobs (num_jobs = local count, scalars global);

@@ -733,7 +733,21 @@ typedef struct {
     uint64_t* bits;
     double* dp;
     int64_t budget, passes;
+    int64_t* rec; /* optional record of the knapsacks run (SW_RRREC_*), NULL: none */
 } rr_t;
+
+/* what twin_reround_arrays_rec records (test infrastructure: tests/shardcases.py) */
+enum {
+    SW_RRREC_RUNS = 0,    /* knapsack DPs run                          */
+    SW_RRREC_CAPMAX,      /* the largest capacity of one               */
+    SW_RRREC_WORDS2,      /* DPs with >= 2 take-bit words per item     */
+    SW_RRREC_CAP512,      /* DPs with capacity >= 512                  */
+    SW_RRREC_REF_CAPMAX,  /* refused: capacity above SW_RR_CAPMAX      */
+    SW_RRREC_REF_WORDS,   /* refused: items x words above SW_RR_WORDS  */
+    SW_RRREC_REF_BUDGET,  /* refused: the solve's item budget is spent */
+    SW_RRREC_LEVELS,      /* the most levels tried in one round        */
+    SW_RRREC_COUNT
+};
 
 static double rr_f(const rr_t* R, int32_t j, int32_t n) {
     return sw_f(&R->jc[j], n, R->nb, R->beta, R->ell, R->slope);
@@ -762,9 +776,21 @@ static int rr_knap(rr_t* R, const uint8_t* cand, int64_t cap, uint8_t* S) {
         for (int32_t i = 0; i < ni; ++i) S[R->items[i]] = 1;
         return 1;
     }
-    if (cap > SW_RR_CAPMAX) return 0;
+    if (cap > SW_RR_CAPMAX) {
+        if (R->rec) R->rec[SW_RRREC_REF_CAPMAX]++;
+        return 0;
+    }
     const int32_t nw = (int32_t)((cap + 64) / 64);
-    if ((int64_t)ni * nw > SW_RR_WORDS || R->budget < ni) return 0;
+    if ((int64_t)ni * nw > SW_RR_WORDS || R->budget < ni) {
+        if (R->rec) R->rec[(int64_t)ni * nw > SW_RR_WORDS ? SW_RRREC_REF_WORDS : SW_RRREC_REF_BUDGET]++;
+        return 0;
+    }
+    if (R->rec) {
+        R->rec[SW_RRREC_RUNS]++;
+        if (cap > R->rec[SW_RRREC_CAPMAX]) R->rec[SW_RRREC_CAPMAX] = cap;
+        R->rec[SW_RRREC_WORDS2] += nw >= 2;
+        R->rec[SW_RRREC_CAP512] += cap >= 512;
+    }
     R->budget -= ni;
     for (int64_t c = 0; c <= cap; ++c) R->dp[c] = 0.0;
     for (int32_t i = 0; i < ni; ++i) {
@@ -838,6 +864,7 @@ static int rr_round(rr_t* R, int32_t t, int32_t* n, uint8_t* y) {
     const double th0 = sw_max(La, sw_from_bits(lo));
     double lvl = th0, prev = 0.0;
     int have_prev = 0;
+    int64_t nlev = 0;
     for (int32_t tried = 0; tried < SW_RR_LEVELS; ++tried) {
         double th = tried == 0 ? th0 : INF;
         if (tried > 0)
@@ -851,6 +878,7 @@ static int rr_round(rr_t* R, int32_t t, int32_t* n, uint8_t* y) {
         have_prev = 1;
         lvl = th;
         R->passes++;
+        if (R->rec && ++nlev > R->rec[SW_RRREC_LEVELS]) R->rec[SW_RRREC_LEVELS] = nlev;
         int ok = 1;
         int64_t wf = 0;
         for (int32_t j = 0; j < N; ++j) {
@@ -886,10 +914,23 @@ static int rr_round(rr_t* R, int32_t t, int32_t* n, uint8_t* y) {
  * returns the number of rounds whose set changed; *passes grows by the
  * rounds visited and the levels tried.  Exported for the sharded CPU engine
  * (oracle/shard_twin.c), which runs it on the gathered placement. */
+int32_t twin_reround_arrays_rec(int32_t N, int32_t T, int32_t G, double k, int32_t nb,
+                                const double* beta, const double* ell, const sw_jobc* jc,
+                                int32_t* n, uint8_t* y, int64_t* passes, int64_t* rec);
+
 int32_t twin_reround_arrays(int32_t N, int32_t T, int32_t G, double k, int32_t nb,
                             const double* beta, const double* ell, const sw_jobc* jc,
                             int32_t* n, uint8_t* y, int64_t* passes) {
+    return twin_reround_arrays_rec(N, T, G, k, nb, beta, ell, jc, n, y, passes, NULL);
+}
+
+/* rec (optional, SW_RRREC_COUNT words, added to): what the knapsacks did —
+ * the caller's own memory, so ranks that run as threads share nothing */
+int32_t twin_reround_arrays_rec(int32_t N, int32_t T, int32_t G, double k, int32_t nb,
+                                const double* beta, const double* ell, const sw_jobc* jc,
+                                int32_t* n, uint8_t* y, int64_t* passes, int64_t* rec) {
     rr_t R;
+    R.rec = rec;
     double slope[SW_BMAX];
     sw_pwl_slopes(nb, beta, ell, slope);
     const size_t NN = N > 0 ? (size_t)N : 1;

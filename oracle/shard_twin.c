@@ -30,7 +30,35 @@ void twin_pack_arrays_caps(int32_t N, int32_t T, int32_t G, const int32_t* w, co
                            const uint64_t* k1, const uint32_t* k2, uint8_t* y, int32_t* placed,
                            const int32_t* caps, int unit);
 
+/*
+ * The record of what one solve placed (tests/shardcases.py launch_forms): the
+ * sizes that select the GPU engine's launch forms.  Rank 0 alone writes it
+ * (the controller is replicated, every rank would write the same gathered
+ * events; ranks may be threads), its own shares only; shard_twin_record
+ * reads it after the solve.  The solve's results do not depend on it.
+ *   words 0..15: [0] words used, [1] events dropped, [2] e_reround calls,
+ *     [3..10] the knapsacks' SW_RRREC_* (plan_twin.c), [11] exchange steps
+ *     run, [12] the most jobs one of them held
+ *   then events of 4 words: {0, V, nsub, shares exist} for an e_pack_share,
+ *     followed by {3, share, jobs, active} per share of rank 0; {1, mode, M,
+ *     active} for an e_pack / e_pack_class (mode 5); {2, width, jobs, active}
+ *     for a class repack inside a share (e_share_repair)
+ */
+#define SHARD_REC_HEAD 16
+#define SHARD_REC_EVENTS 8192
+#define SHARD_REC_RR 8
+static int64_t g_rec[SHARD_REC_HEAD + 4 * SHARD_REC_EVENTS];
+
+static void rec_event(int64_t* rec, int64_t kind, int64_t a, int64_t b, int64_t c) {
+    if (!rec) return;
+    if (rec[0] + 4 > SHARD_REC_HEAD + 4 * SHARD_REC_EVENTS) { rec[1]++; return; }
+    int64_t* e = rec + rec[0];
+    e[0] = kind; e[1] = a; e[2] = b; e[3] = c;
+    rec[0] += 4;
+}
+
 typedef struct {
+    int64_t* rec; /* rank 0: g_rec, else NULL */
     const sw_host_comm* comm;
     int32_t rank, world, LW;
     int64_t N, off, q, P; /* global jobs, slice offset, jobs per lane, padded slice */
@@ -424,6 +452,11 @@ static int e_pack_any(eng_t* E, int32_t mode, int32_t src, double Mb, int32_t yd
         k1[j] = all[j].k1;
         k2[j] = all[j].k2;
     }
+    if (E->rec) {
+        int64_t act = 0;
+        for (int64_t j = 0; j < N; ++j) act += nin[j] > 0;
+        rec_event(E->rec, 1, mode, P * E->world, act);
+    }
     twin_pack_arrays_caps((int32_t)N, E->T, E->G, E->w_all, nin, k1, k2, y, placed,
                           mode == 5 ? caps : NULL, mode == 5);
     for (int32_t i = 0; i < E->NL; ++i) {
@@ -525,6 +558,13 @@ static int e_pack_share(void* ctx, int32_t src, int32_t ydst, int32_t pdst) {
         nin[i] = E->share ? E->arr[src][i] : 0;
         k1[i] = nin[i] > 0 ? sw_ratio_key(E->p[i] / (double)(nin[i] * w[i])) : 0;
     }
+    rec_event(E->rec, 0, V, S, E->share);
+    for (int32_t s = 0; E->rec && s < S; ++s) {
+        int64_t act = 0;
+        e_shares(E, s, &lo, &hi);
+        for (int32_t i = lo; i < hi; ++i) act += nin[i] > 0;
+        rec_event(E->rec, 3, s, hi - lo, act);
+    }
     if (E->share)
         for (int32_t s = 0; s < S; ++s) {
             e_shares(E, s, &lo, &hi);
@@ -585,6 +625,11 @@ static int e_share_repair_one(eng_t* E, int32_t src, int32_t ydst, int32_t pdst,
             const int cls = E->arr[src][lo + i] > 0 && w[i] == R.wc[c];
             nc[i] = cls ? E->arr[src][lo + i] : 0;
             k1[i] = cls ? sw_ratio_key(E->p[lo + i] / (double)nc[i]) : 0;
+        }
+        if (E->rec) {
+            int64_t act = 0;
+            for (int32_t i = 0; i < NL; ++i) act += nc[i] > 0;
+            rec_event(E->rec, 2, R.wc[c], NL, act);
         }
         twin_pack_arrays_caps(NL, T, E->G, w, nc, k1, k2, yc, pc, R.caps[c], 1);
         for (int32_t i = 0; i < NL; ++i) {
@@ -649,6 +694,10 @@ static int e_p2x(void* ctx, int32_t ysrc, int32_t nsrc, int32_t* cancels) {
         m[A] = all[j].m;
         ++A;
     }
+    if (E->rec) {
+        E->rec[11]++;
+        if (A > E->rec[12]) E->rec[12] = A;
+    }
     *cancels = twin_p2x_run(A, E->T, E->G, job, w, c, m);
     for (int32_t a = 0; a < A; ++a)
         if (job[a] >= E->off && job[a] < E->off + E->NL) E->y[ysrc][job[a] - E->off] = m[a];
@@ -658,9 +707,9 @@ out:
 }
 
 /* the per-round re-optimisation on the gathered P1 plan (twin_reround_arrays) */
-int32_t twin_reround_arrays(int32_t N, int32_t T, int32_t G, double k, int32_t nb,
-                            const double* beta, const double* ell, const sw_jobc* jc,
-                            int32_t* n, uint8_t* y, int64_t* passes);
+int32_t twin_reround_arrays_rec(int32_t N, int32_t T, int32_t G, double k, int32_t nb,
+                                const double* beta, const double* ell, const sw_jobc* jc,
+                                int32_t* n, uint8_t* y, int64_t* passes, int64_t* rec);
 typedef struct {
     sw_jobc c;
     uint64_t m;
@@ -691,8 +740,9 @@ static int e_reround(void* ctx, int32_t* moves) {
         for (int32_t t = 0; t < E->T; ++t) y[(size_t)j * E->T + t] = (uint8_t)((all[j].m >> t) & 1u);
     }
     int64_t passes = 0;
-    *moves = twin_reround_arrays((int32_t)N, E->T, E->G, E->k, E->nb, E->beta, E->ell, jc, n, y,
-                                 &passes);
+    if (E->rec) E->rec[2]++;
+    *moves = twin_reround_arrays_rec((int32_t)N, E->T, E->G, E->k, E->nb, E->beta, E->ell, jc, n, y,
+                                     &passes, E->rec ? E->rec + 3 : NULL);
     for (int32_t i = 0; i < E->NL; ++i) {
         const int64_t j = E->off + i;
         uint64_t m = 0;
@@ -719,6 +769,11 @@ int shard_twin_solve(const sw_host_comm* comm, int32_t rank, int32_t world, cons
     eng_t E;
     memset(&E, 0, sizeof(E));
     E.comm = comm;
+    if (rank == 0) {
+        memset(g_rec, 0, sizeof(int64_t) * SHARD_REC_HEAD);
+        g_rec[0] = SHARD_REC_HEAD;
+        E.rec = g_rec;
+    }
     E.rank = rank;
     E.world = world;
     E.LW = SW_DET_LANES / world;
@@ -862,4 +917,12 @@ int shard_share_caps(const int64_t* loads, int32_t W, int32_t rank, int32_t T, i
 uint64_t shard_search_resolve(uint64_t lo, uint64_t hi, int64_t chi, int64_t bud, const uint64_t* v,
                               const int64_t* w, int32_t n) {
     return sw_search_resolve(lo, hi, chi, bud, v, w, n);
+}
+
+/* The record of the last solve whose rank 0 ran in this process (the layout
+ * above): copies up to cap words to out, returns the words the record holds. */
+int64_t shard_twin_record(int64_t* out, int64_t cap) {
+    const int64_t n = g_rec[0];
+    for (int64_t i = 0; i < n && i < cap; ++i) out[i] = g_rec[i];
+    return n;
 }

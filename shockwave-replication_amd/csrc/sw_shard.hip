@@ -3203,6 +3203,11 @@ int pack_any(sw_shard_state* S, int32_t mode, int32_t src, double Mb, int32_t yd
             if (M > 32 * SW_BLOCK) SW_LAUNCH_PACK(64, SW_BLOCK, 8 * SW_BLOCK);
             else SW_LAUNCH_PACK(32, SW_BLOCK, 8 * SW_BLOCK);
         }
+    } else if (local && jhi - (int64_t)jlo <= 20 * SW_BLOCK) {
+        /* a class repack inside one share (op_share_repair at world 1, above
+         * 32,768 jobs): the entries are this rank's, the active ones lie in
+         * the share's jobs [jlo, jhi) — at most 8,192 of them (sw_share_count) */
+        SW_LAUNCH_SEL(SW_BLOCK, 20, lo);
     } else {
         return S->h->err = "sharded placement holds at most 32768 jobs", SW_ERR_CAPACITY;
     }
