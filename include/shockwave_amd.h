@@ -382,6 +382,49 @@ int sw_mmf_allocate_types(sw_handle* h, int32_t num_jobs, int32_t num_types, con
                           double* level);
 
 /*
+ * The same LP as sw_mmf_allocate_types, with the allocation the reference's
+ * ECOS converges to (csrc/sw_mmf_ipm.h, a primal–dual interior-point method,
+ * one kernel launch per call).  level[0] receives the LP's optimal level t*,
+ * level[1] the Newton steps taken.  allocation receives the ANALYTIC CENTRE OF
+ * THE OPTIMAL FACE: the maximiser of Σ log(slack) over the face {the LP's
+ * constraints, t = t*}, the sum over every inequality (value, capacity and
+ * time rows, x ≥ 0, t ≥ 0) that is not tight on the whole face — the limit of
+ * the LP's central path.  For one type it is the point sw_mmf_allocate returns.
+ *   A type with 0 workers gets shares of exactly 0.0.  If a job has no positive
+ * coefficient on any type that has workers the level is exactly 0.0 and the
+ * allocation is still the centre by the definition above (t is pinned at 0,
+ * that job's value row is tight on the whole face).
+ *   Tolerances, as measured against an independent computation of the centre
+ * (tests/test_mmf_centre.py; coefficients 0 or within [0.2, 4]·scale factor):
+ * shares within 1e-6 of the centre (measured ≤ 4.6e-9), the level within
+ * 1e-6·max(1, t*) of HiGHS (measured ≤ 1.2e-11; one type: 2.3e-13 relative),
+ * shares of identical types equal to 1e-8 (measured ≤ 7e-15).  The method
+ * follows the central path to μ = 2e-8·min(1, t) and a quarter of it (t the
+ * level over the largest coefficient's power of two) and extrapolates to
+ * μ = 0.  With coefficients spread over six decades the level still came out
+ * within 8e-7 of its own size; the shares have no independent reference there
+ * (DESIGN.md §12).
+ *   Validation as sw_mmf_allocate_types: a non-finite or negative coefficient,
+ * a scale factor outside [1, 255] or a negative worker count is
+ * SW_ERR_INVALID.  Limits: 1 ≤ num_types ≤ 16, num_jobs ≤ 16384 per instance
+ * (SW_ERR_INVALID); there is no tableau, hence no 256 MB cap.  A step cap
+ * (SW_ERR_CAPACITY) guards the iteration.  num_jobs = 0 is a no-op.
+ *   The batch form takes `count` instances over one num_types in the CSR
+ * convention of sw_ftf_allocate_batch (instance i is jobs offsets[i] …
+ * offsets[i+1]; empty instances are allowed and give levels (0, 0)), workers
+ * [count][num_types], levels [count][2], and runs in one launch; every
+ * instance's result is bit for bit that of the single call.  count = 0 is a
+ * no-op.  sw_abi_version stays 2.
+ */
+int sw_mmf_allocate_types_centred(sw_handle* h, int32_t num_jobs, int32_t num_types,
+                                  const int32_t* workers, const int32_t* scale_factors,
+                                  const double* coefficients, double* allocation, double* level);
+int sw_mmf_allocate_types_centred_batch(sw_handle* h, int32_t count, int32_t num_types,
+                                        const int64_t* offsets, const int32_t* workers,
+                                        const int32_t* scale_factors, const double* coefficients,
+                                        double* allocation, double* levels);
+
+/*
  * The Gavel FinishTimeFairness (Themis) baseline's allocation program
  * (policies/finish_time_fairness.py:55-140) for one worker type, or several
  * with identical throughputs:

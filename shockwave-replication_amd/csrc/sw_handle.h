@@ -136,6 +136,8 @@ struct sw_handle {
     sw_shard_state* shard = nullptr;
     /* MaxMinFairness allocation buffers (sw_mmf.hip) */
     void* mmf = nullptr;
+    /* the workspace of the centred worker-type MaxMinFairness call (sw_mmf_ipm.hip) */
+    void* mmfc = nullptr;
     /* the blocks of the per-job allocation policies (sw_alloc.h) and of AlloX (sw_allox.hip) */
     sw_io_bufs io;
 };
@@ -157,6 +159,8 @@ inline int sw_fail(sw_handle* h, int code, const std::string& msg) {
 void sw_shard_release(sw_handle* h);
 /* sw_mmf.hip: frees the MaxMinFairness buffers */
 void sw_mmf_release(sw_handle* h);
+/* sw_mmf_ipm.hip: frees the centred call's workspace */
+void sw_mmfc_release(sw_handle* h);
 /* frees the shared input / output blocks */
 inline void sw_io_release(sw_handle* h) {
     h->io.in.release(); h->io.out.release(); h->io.hin.release(); h->io.hout.release();

@@ -13,7 +13,11 @@ replaced by
   * several worker types: ``sw_mmf_allocate_types`` — the same LP solved
     exactly by the simplex method on the GPU: the LP's optimal level, and an
     optimal vertex as the allocation (ECOS returns an interior point of the
-    same optimal face, so the shares agree only where the optimum is unique).
+    same optimal face, so the shares agree only where the optimum is unique);
+  * several worker types with ``centred=True``:
+    ``sw_mmf_allocate_types_centred`` — the same LP by an interior-point
+    method on the GPU: the LP's level, and the analytic centre of its optimal
+    face, the point ECOS converges to.  No warning; not yet the default.
 
 The result is clipped to [0, 1] as ``x.value.clip(min=0.0).clip(max=1.0)``
 (max_min_fairness.py:100).  A native error raises; there is no CPU fallback.
@@ -72,10 +76,11 @@ def _proportional_throughputs(throughputs, worker_types, cluster_spec):
 class MaxMinFairnessPolicyWithPerf:
     """max_min_fairness.py:37-100 (heterogeneity-aware: real throughputs)."""
 
-    def __init__(self, solver="ECOS", native=None):
+    def __init__(self, solver="ECOS", native=None, centred=False):
         self._name = "MaxMinFairness_Perf"
         self._solver = solver  # kept for the signature; the LP runs on the GPU
         self._native = native
+        self._centred = centred  # several types: the face's analytic centre, not a vertex
 
     def _engine(self):
         if self._native is None:
@@ -110,6 +115,8 @@ class MaxMinFairnessPolicyWithPerf:
         if coef.shape[1] == 1 and (coef > 0.0).all():
             x, _, _ = eng.mmf_allocate(sf, coef[:, 0], int(num_workers[0]))
             x = x.reshape(-1, 1)
+        elif self._centred:
+            x, _, _ = eng.mmf_allocate_types_centred(num_workers, sf, coef)
         else:
             global _WARNED
             if not _WARNED:
@@ -126,9 +133,9 @@ class MaxMinFairnessPolicy:
     """max_min_fairness.py:12-34: the WithPerf policy with every throughput 1.0
     (the Fig-9 "gavel" baseline)."""
 
-    def __init__(self, solver="ECOS", native=None):
+    def __init__(self, solver="ECOS", native=None, centred=False):
         self._name = "MaxMinFairness"
-        self._max_min_fairness_perf_policy = MaxMinFairnessPolicyWithPerf(solver, native)
+        self._max_min_fairness_perf_policy = MaxMinFairnessPolicyWithPerf(solver, native, centred)
 
     def get_allocation(self, unflattened_throughputs, scale_factors, priority_weights, cluster_spec):
         if not unflattened_throughputs:

@@ -320,7 +320,8 @@ EXPORTED_SYMBOLS = (
     "sw_mmf_allocate_types", "sw_batch_keep_masks", "sw_ftf_allocate", "sw_ftf_allocate_batch",
     "sw_wf_allocate", "sw_wf_allocate_batch", "sw_mtd_allocate", "sw_mtd_allocate_batch",
     "sw_mst_allocate", "sw_mst_allocate_batch", "sw_allox_assign", "sw_allox_assign_batch",
-    "sw_wfh_allocate", "sw_wfh_allocate_batch",
+    "sw_wfh_allocate", "sw_wfh_allocate_batch", "sw_mmf_allocate_types_centred",
+    "sw_mmf_allocate_types_centred_batch",
 )
 
 
@@ -408,6 +409,11 @@ def load(path: str | None = None):
     lib.sw_mmf_allocate.restype = C.c_int
     lib.sw_mmf_allocate_types.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip, _ip, _dp, _dp, _dp]
     lib.sw_mmf_allocate_types.restype = C.c_int
+    lib.sw_mmf_allocate_types_centred.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip, _ip, _dp, _dp, _dp]
+    lib.sw_mmf_allocate_types_centred.restype = C.c_int
+    lib.sw_mmf_allocate_types_centred_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), _ip,
+                                                        _ip, _dp, _dp, _dp]
+    lib.sw_mmf_allocate_types_centred_batch.restype = C.c_int
     for name, (dtypes, _, _) in _ALLOC.items():
         cols = [_ip if t is np.int32 else _dp for t in dtypes]
         single, batch = getattr(lib, f"sw_{name}_allocate"), getattr(lib, f"sw_{name}_allocate_batch")
@@ -563,6 +569,54 @@ class Solver:
                                                    x.ctypes.data_as(_dp), lvl.ctypes.data_as(_dp)),
                     "sw_mmf_allocate_types")
         return x, float(lvl[0]), int(lvl[1])
+
+    @staticmethod
+    def _mmf_types_arrays(workers, scale_factors, coefficients):
+        w = np.ascontiguousarray(workers, dtype=np.int32)
+        sf = np.ascontiguousarray(scale_factors, dtype=np.int32)
+        c = np.ascontiguousarray(coefficients, dtype=np.float64)
+        if c.ndim != 2 or c.shape != (len(sf), len(w)):
+            raise ValueError("coefficients must be [num_jobs][num_types]")
+        return w, sf, c
+
+    def mmf_allocate_types_centred(self, workers, scale_factors, coefficients):
+        """The LP of mmf_allocate_types with the analytic centre of its optimal
+        face as the allocation, the point ECOS converges to
+        (sw_mmf_allocate_types_centred); returns (x [m, n], t*, Newton steps)."""
+        w, sf, c = self._mmf_types_arrays(workers, scale_factors, coefficients)
+        x = np.zeros(c.shape, dtype=np.float64)
+        lvl = np.zeros(2, dtype=np.float64)
+        self._check(self.lib.sw_mmf_allocate_types_centred(self.h, c.shape[0], c.shape[1], w.ctypes.data_as(_ip),
+                                                           sf.ctypes.data_as(_ip), c.ctypes.data_as(_dp),
+                                                           x.ctypes.data_as(_dp), lvl.ctypes.data_as(_dp)),
+                    "sw_mmf_allocate_types_centred")
+        return x, float(lvl[0]), int(lvl[1])
+
+    def mmf_allocate_types_centred_batch(self, instances, offsets=None):
+        """sw_mmf_allocate_types_centred_batch over a list of (workers,
+        scale_factors, coefficients) tuples with one number of types, one kernel
+        launch; returns the list of (x [m, n], t*, Newton steps).  offsets
+        (tests only) overrides the CSR offsets built from the instances."""
+        parts = [self._mmf_types_arrays(*inst) for inst in instances]
+        count = len(parts)
+        n = len(parts[0][0]) if parts else 1
+        if any(len(w) != n for w, _, _ in parts):
+            raise ValueError("every instance must have the same number of worker types")
+        off = np.zeros(count + 1, dtype=np.int64)
+        for i, (_, sf, _) in enumerate(parts):
+            off[i + 1] = off[i] + len(sf)
+        w = np.ascontiguousarray(np.concatenate([p[0] for p in parts]) if parts else [], dtype=np.int32)
+        sf = np.ascontiguousarray(np.concatenate([p[1] for p in parts]) if parts else [], dtype=np.int32)
+        c = np.ascontiguousarray(np.concatenate([p[2].reshape(-1) for p in parts]) if parts else [], dtype=np.float64)
+        x = np.zeros(len(c), dtype=np.float64)
+        lvl = np.zeros((count, 2), dtype=np.float64)
+        coff = off if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
+        self._check(self.lib.sw_mmf_allocate_types_centred_batch(
+            self.h, count, n, coff.ctypes.data_as(C.POINTER(C.c_int64)), w.ctypes.data_as(_ip),
+            sf.ctypes.data_as(_ip), c.ctypes.data_as(_dp), x.ctypes.data_as(_dp), lvl.ctypes.data_as(_dp)),
+            "sw_mmf_allocate_types_centred_batch")
+        return [(x[off[i] * n:off[i + 1] * n].reshape(-1, n).copy(), float(lvl[i, 0]), int(lvl[i, 1]))
+                for i in range(count)]
 
     # ---- the per-job allocation policies (csrc/sw_alloc.h; _ALLOC above) ----
     @staticmethod
