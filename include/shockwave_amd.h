@@ -616,6 +616,51 @@ int sw_mtd_allocate_batch(sw_handle* h, int32_t count, const int64_t* offsets,
                           const double* full_time, double* allocation, double* levels);
 
 /*
+ * MinTotalDuration over worker types whose throughputs DIFFER: the reference's
+ * program (policies/min_total_duration.py:41-106) with throughputs
+ * [num_jobs][num_types] and steps [num_jobs] (steps remaining, ≥ 0; a job with
+ * 0 steps is "dead": it bounds no T but keeps its rows), in one launch
+ * (csrc/sw_mtd_types.h, sw_mtd_types.hip).
+ *   The reference's LP is feasible at T exactly when T·t* ≥ 1, t* the max-min
+ * level of Σ_k (throughput_jk / steps_j)·x_jk over the jobs with steps left,
+ * under Σ_j scale_factor_j·x_jk ≤ workers_k, Σ_k x_jk ≤ 1, x ≥ 0.  The call
+ * computes t* once by the interior-point method of
+ * sw_mmf_allocate_types_centred, replays the reference's probe sequence on it
+ * (the search of sw_mtd_allocate), and returns the ANALYTIC CENTRE of the
+ * reference's LP at the found T: the maximiser of Σ log(slack) over its value
+ * rows (dead jobs' included, right side 0), capacity rows, time rows and
+ * x ≥ 0, without the inequalities tight on the whole polytope.  A type with 0
+ * workers gets shares of exactly 0.0.
+ *   result[4] = T, t* (1/seconds; 0.0 without a live job), Newton steps of
+ * both phases, flags: SW_MTDT_IDLE = 1 (no job has steps left: T is the last
+ * midpoint above 100), SW_MTDT_THIN_FLAG = 2 (T·t* − 1 is below 1e-7: the
+ * polytope at T is too thin to centre in, the allocation is the centre of the
+ * level LP's optimal face instead, feasible at T up to the level's error).
+ *   Tolerances, as measured against an independent computation (HiGHS, a
+ * replay of the search, a null-space Newton centre; tests/test_mtd_types.py):
+ * T equal to the replay's on every instance whose probes keep 1e-5 relative
+ * from 1/t*; shares within 1e-6 of the centre where T·t* − 1 ≥ 1e-3 (measured
+ * ≤ 1.8e-10); every row of the LP within 1e-9 relative.
+ *   SW_ERR_INVALID: a scale factor outside [1, 255], a negative worker count,
+ * a non-finite or negative throughput or steps, num_types outside [1, 16],
+ * num_jobs above 16384, a job with steps left and no positive throughput on a
+ * type that has workers (the reference never returns there), or whose best
+ * full time steps / max_k throughput exceeds 1e15 seconds.  A step cap or a
+ * non-positive pivot is SW_ERR_CAPACITY.  num_jobs = 0 is a no-op with result
+ * (0, 0, 0, 0).
+ *   The batch form takes `count` instances over one num_types in the CSR
+ * convention of sw_mtd_allocate_batch, workers [count][num_types], results
+ * [count][4]; every instance's result is bit for bit that of the single call.
+ * sw_abi_version stays 2.
+ */
+int sw_mtd_allocate_types(sw_handle* h, int32_t num_jobs, int32_t num_types, const int32_t* workers,
+                          const int32_t* scale_factors, const double* throughputs, const double* steps,
+                          double* allocation, double* result);
+int sw_mtd_allocate_types_batch(sw_handle* h, int32_t count, int32_t num_types, const int64_t* offsets,
+                                const int32_t* workers, const int32_t* scale_factors, const double* throughputs,
+                                const double* steps, double* allocation, double* results);
+
+/*
  * The Gavel max-sum-throughput baseline's allocation ("MST";
  * policies/max_sum_throughput.py:39-96, selected as max_sum_throughput_perf in
  * utils.get_policy) for one worker type.  The reference solves, with ECOS,

@@ -117,10 +117,20 @@ typedef struct {
 
 /* The per-job workspace, structure of arrays: field f of job j at
  * ws[f·stride + j].  Fields: c, x, s, dx, ds, d, h per active type, then the
- * scalars below: 7·na + SW_IPM_NSCAL doubles per job. */
+ * scalars below: 8·na + SW_IPM_NSCAL doubles per job.
+ *   SW_IPM_KAP is κ_j, the coefficient of t in the job's value row
+ * (κ_j·t ≤ Σ_k c·x): 1.0 for every job of the MaxMinFairness program, so that
+ * each product with it is exact and that program's bits are what they were
+ * before κ existed; 0.0 for a row that does not bound the level (a job without
+ * remaining steps in sw_mtd_types.h).  SW_IPM_RSC is the power of two by which
+ * the residuals of the job's value row and of its shares' dual equations are
+ * multiplied before they are held against SW_IPM_RES: 1.0 here, where every
+ * coefficient is below 2; 1/(the row's largest coefficient) where rows are
+ * larger (sw_mtd_types.h), whose residuals' rounding grows with it.  With has_t = 0, g->t is a constant of
+ * the rows: 0.0 here, the fixed level of sw_mtd_types.h's second phase. */
 enum { SW_IPM_U, SW_IPM_SU, SW_IPM_V, SW_IPM_SV, SW_IPM_DU, SW_IPM_DSU, SW_IPM_DV, SW_IPM_DSV,
        SW_IPM_DDU, SW_IPM_DDV, SW_IPM_HU, SW_IPM_HV, SW_IPM_RHOV, SW_IPM_RHOT, SW_IPM_DET, SW_IPM_HASV,
-       SW_IPM_NSCAL };
+       SW_IPM_KAP, SW_IPM_RSC, SW_IPM_NSCAL };
 #define SW_IPM_FIELDS(n) (8 * (n) + SW_IPM_NSCAL)
 
 typedef struct {
@@ -179,6 +189,8 @@ SW_HD void sw_ipm_job_load(const sw_ipm_glob* g, sw_ipm_job* J, const double* co
         mx = sw_max(mx, c);
     }
     SW_IPM_Q(J, SW_IPM_HASV) = mx > 0.0 ? 1.0 : 0.0;
+    SW_IPM_Q(J, SW_IPM_KAP) = 1.0;
+    SW_IPM_Q(J, SW_IPM_RSC) = 1.0;
     sums[0] = J->sf;
     sums[1] = mx > 0.0 ? 1.0 : 0.0;
     maxes[0] = -mx;
@@ -197,7 +209,8 @@ SW_HD void sw_ipm_glob_load(sw_ipm_glob* g, const double* sums, const double* ma
 }
 
 /* Init pass 2: x = θ; max: [0] −(the job's value Σ c·x), −∞-free: a job without
- * a value row gives −DBL_MAX so that it never sets the minimum. */
+ * a value row, or whose row does not hold t (κ = 0), gives −DBL_MAX so that it
+ * never sets the minimum. */
 SW_HD void sw_ipm_job_start(const sw_ipm_glob* g, sw_ipm_job* J, double* maxes) {
     double val = 0.0;
     for (int32_t k = 0; k < J->na; ++k) {
@@ -205,7 +218,7 @@ SW_HD void sw_ipm_job_start(const sw_ipm_glob* g, sw_ipm_job* J, double* maxes) 
         val = val + SW_IPM_C(J, k) * g->theta[k];
     }
     SW_IPM_Q(J, SW_IPM_U) = val;
-    maxes[0] = SW_IPM_Q(J, SW_IPM_HASV) != 0.0 ? -val : -1.7976931348623157e308;
+    maxes[0] = SW_IPM_Q(J, SW_IPM_HASV) != 0.0 && SW_IPM_Q(J, SW_IPM_KAP) != 0.0 ? -val : -1.7976931348623157e308;
 }
 
 SW_HD void sw_ipm_glob_start(sw_ipm_glob* g, const double* maxes) {
@@ -229,7 +242,7 @@ SW_HD void sw_ipm_job_start2(const sw_ipm_glob* g, sw_ipm_job* J) {
         mx = sw_max(mx, SW_IPM_C(J, k));
     }
     const double sv = 1.0 + mx * su;
-    SW_IPM_Q(J, SW_IPM_U) = hasv ? SW_IPM_Q(J, SW_IPM_U) - g->t : 0.0;
+    SW_IPM_Q(J, SW_IPM_U) = hasv ? SW_IPM_Q(J, SW_IPM_U) - SW_IPM_Q(J, SW_IPM_KAP) * g->t : 0.0;
     SW_IPM_Q(J, SW_IPM_SU) = su;
     SW_IPM_Q(J, SW_IPM_V) = 1.0 - sx;
     SW_IPM_Q(J, SW_IPM_SV) = sv;
@@ -241,7 +254,7 @@ SW_HD double sw_ipm_rpv(const sw_ipm_glob* g, const sw_ipm_job* J) {
     double val = 0.0;
     if (SW_IPM_Q(J, SW_IPM_HASV) == 0.0) return 0.0;
     for (int32_t k = 0; k < J->na; ++k) val = val + SW_IPM_C(J, k) * SW_IPM_X(J, k);
-    return val - g->t - SW_IPM_Q(J, SW_IPM_U);
+    return val - SW_IPM_Q(J, SW_IPM_KAP) * g->t - SW_IPM_Q(J, SW_IPM_U);
 }
 SW_HD double sw_ipm_rpt(const sw_ipm_job* J) {
     double sx = 0.0;
@@ -252,7 +265,7 @@ SW_HD double sw_ipm_rd(const sw_ipm_glob* g, const sw_ipm_job* J, int32_t k) {
     return SW_IPM_Q(J, SW_IPM_SV) + J->sf * g->sw[k] - SW_IPM_C(J, k) * SW_IPM_Q(J, SW_IPM_SU) - SW_IPM_S(J, k);
 }
 
-/* Pass A.  Sums: [k] sf·x_k (k < na), [na] Σ z·s of the job, [na+1] s_u.
+/* Pass A.  Sums: [k] sf·x_k (k < na), [na] Σ z·s of the job, [na+1] κ·s_u.
  * Maxes: [0] primal residual, [1] dual residual, [2] |z·s/μ_end − 1|. */
 SW_HD void sw_ipm_job_resid(const sw_ipm_glob* g, const sw_ipm_job* J, double* sums, double* maxes) {
     const int hasv = SW_IPM_Q(J, SW_IPM_HASV) != 0.0;
@@ -263,7 +276,7 @@ SW_HD void sw_ipm_job_resid(const sw_ipm_glob* g, const sw_ipm_job* J, double* s
         sums[k] = J->sf * SW_IPM_X(J, k);
         comp = comp + p;
         dev = sw_max(dev, sw_ipm_abs(p * ime - 1.0));
-        dinf = sw_max(dinf, sw_ipm_abs(sw_ipm_rd(g, J, k)));
+        dinf = sw_max(dinf, sw_ipm_abs(sw_ipm_rd(g, J, k)) * SW_IPM_Q(J, SW_IPM_RSC));
     }
     {
         const double p = SW_IPM_Q(J, SW_IPM_V) * SW_IPM_Q(J, SW_IPM_SV);
@@ -276,8 +289,8 @@ SW_HD void sw_ipm_job_resid(const sw_ipm_glob* g, const sw_ipm_job* J, double* s
         dev = sw_max(dev, sw_ipm_abs(p * ime - 1.0));
     }
     sums[J->na] = comp;
-    sums[J->na + 1] = SW_IPM_Q(J, SW_IPM_SU);
-    maxes[0] = sw_max(sw_ipm_abs(sw_ipm_rpv(g, J)), sw_ipm_abs(sw_ipm_rpt(J)));
+    sums[J->na + 1] = SW_IPM_Q(J, SW_IPM_KAP) * SW_IPM_Q(J, SW_IPM_SU);
+    maxes[0] = sw_max(sw_ipm_abs(sw_ipm_rpv(g, J)) * SW_IPM_Q(J, SW_IPM_RSC), sw_ipm_abs(sw_ipm_rpt(J)));
     maxes[1] = dinf;
     maxes[2] = dev;
 }
@@ -378,7 +391,7 @@ SW_HD void sw_ipm_job_prep(const sw_ipm_glob* g, sw_ipm_job* J) {
         const double u = SW_IPM_Q(J, SW_IPM_U), su = SW_IPM_Q(J, SW_IPM_SU), hu = tg / su - u;
         SW_IPM_Q(J, SW_IPM_DDU) = u / su;
         SW_IPM_Q(J, SW_IPM_HU) = hu;
-        /* row: t − Σ c·x + u = 0, so r_p = Σ c·x − t − u */
+        /* row: κ·t − Σ c·x + u = 0, so r_p = Σ c·x − κ·t − u */
         SW_IPM_Q(J, SW_IPM_RHOV) = sw_ipm_rpv(g, J) + sch - hu;
     } else {
         SW_IPM_Q(J, SW_IPM_DDU) = 0.0;
@@ -390,7 +403,7 @@ SW_HD void sw_ipm_job_prep(const sw_ipm_glob* g, sw_ipm_job* J) {
 
 /* What the values of row k share: B⁻¹·E_k = sf·d_k·(α, β)/det. */
 typedef struct {
-    double alpha, beta, e, b, det, dk, ck;
+    double alpha, beta, e, b, det, dk, ck, kap;
     int32_t k, hasv;
 } sw_ipm_rowctx;
 
@@ -401,6 +414,7 @@ SW_HD sw_ipm_rowctx sw_ipm_row_begin(const sw_ipm_job* J, int32_t k) {
     r.det = SW_IPM_Q(J, SW_IPM_DET);
     r.dk = SW_IPM_D(J, k);
     r.ck = SW_IPM_C(J, k);
+    r.kap = SW_IPM_Q(J, SW_IPM_KAP);
     double sd = 0.0, scd = 0.0, al = 0.0, be = 0.0;
     for (int32_t i = 0; i < J->na; ++i) {
         const double di = SW_IPM_D(J, i), ci = SW_IPM_C(J, i);
@@ -442,13 +456,13 @@ SW_HD double sw_ipm_row_val(const sw_ipm_job* J, const sw_ipm_rowctx* r, int32_t
     if (i == 0) return sf * sf * r->dk * sw_ipm_det(J, k) / r->det;
     if (i < na - k) /* −S_kl, l = k + i */
         return sf * sf * r->dk * SW_IPM_D(J, k + i) * sw_ipm_gamma(J, r, k + i) / r->det;
-    if (i == na - k) return r->hasv ? sf * r->dk * r->alpha / r->det : 0.0;
+    if (i == na - k) return r->hasv ? r->kap * (sf * r->dk * r->alpha / r->det) : 0.0;
     if (i == na - k + 1)
         return sf * SW_IPM_H(J, k) +
                sf * r->dk * (SW_IPM_Q(J, SW_IPM_RHOV) * r->alpha + SW_IPM_Q(J, SW_IPM_RHOT) * r->beta) / r->det;
     if (!r->hasv) return 0.0;
-    if (i == na - k + 2) return r->e / r->det;
-    return (r->e * SW_IPM_Q(J, SW_IPM_RHOV) - r->b * SW_IPM_Q(J, SW_IPM_RHOT)) / r->det;
+    if (i == na - k + 2) return r->kap * r->kap * (r->e / r->det);
+    return r->kap * ((r->e * SW_IPM_Q(J, SW_IPM_RHOV) - r->b * SW_IPM_Q(J, SW_IPM_RHOT)) / r->det);
 }
 
 /* After pass R_k (one thread): row k of the reduced system. */
@@ -537,7 +551,7 @@ SW_HD void sw_ipm_glob_solve(sw_ipm_glob* g) {
 SW_HD void sw_ipm_job_back(const sw_ipm_glob* g, sw_ipm_job* J, double* maxes) {
     const int hasv = SW_IPM_Q(J, SW_IPM_HASV) != 0.0;
     const double sf = J->sf, det = SW_IPM_Q(J, SW_IPM_DET);
-    const double rv = SW_IPM_Q(J, SW_IPM_RHOV) - g->dt, rt = SW_IPM_Q(J, SW_IPM_RHOT);
+    const double rv = SW_IPM_Q(J, SW_IPM_RHOV) - SW_IPM_Q(J, SW_IPM_KAP) * g->dt, rt = SW_IPM_Q(J, SW_IPM_RHOT);
     const double ddu = SW_IPM_Q(J, SW_IPM_DDU), ddv = SW_IPM_Q(J, SW_IPM_DDV);
     double nv = ddv * rv, nt = hasv ? ddu * rt : rt;
     double rp = 0.0, rd = 0.0;
@@ -642,7 +656,7 @@ SW_HD void sw_ipm_job_final(const sw_ipm_glob* g, const sw_ipm_job* J, double* s
         r = sw_max(r, -e / SW_IPM_X(J, k));
     }
     r = sw_max(r, se / SW_IPM_Q(J, SW_IPM_V));
-    r = sw_max(r, (dte - sce) / SW_IPM_Q(J, SW_IPM_U));
+    if (SW_IPM_Q(J, SW_IPM_HASV) != 0.0) r = sw_max(r, (SW_IPM_Q(J, SW_IPM_KAP) * dte - sce) / SW_IPM_Q(J, SW_IPM_U));
     maxes[0] = r;
 }
 

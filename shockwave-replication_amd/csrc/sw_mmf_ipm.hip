@@ -12,7 +12,7 @@
  * chunk [L·q, (L+1)·q) of the deterministic sum (q = ⌈m/512⌉), so the CPU twin
  * (tests/twins/mmfc_twin.c) returns the same bits.
  *
- *   per job    x, s, the slacks, their steps and scalings: 8·na + 16 doubles in
+ *   per job    x, s, the slacks, their steps and scalings: 8·na + 18 doubles in
  *              a workspace on the handle (HBM, L2-resident at these sizes),
  *              structure of arrays
  *   LDS        sw_ipm_glob (t, the capacity slacks, the reduced system: 4 KB)
@@ -26,6 +26,7 @@
  *              pass D (the step)                fused with the next pass A
  *   the end    the two points of the path extrapolated to μ = 0 under a ratio
  *              test                             1 reduction of na sums, 1 max
+ * The reduction's helpers are in sw_mmf_ipm_dev.h (shared with sw_mtd_types.hip).
  * A reduction is the block's deterministic tree for sums (wave_dettree, then
  * the halving tree over the eight waves) and exact maxima, two barriers: one
  * before thread 0 combines the waves' values and runs the one-thread part of
@@ -43,75 +44,9 @@
 #include "sw_block.h"
 #include "sw_handle.h"
 #include "sw_mmf_ipm.h"
+#include "sw_mmf_ipm_dev.h"
 
 namespace {
-
-constexpr double kNegHuge = -1.7976931348623157e308;
-
-struct IpmRed {
-    double s[SW_WAVES][SW_IPM_NRED];
-    double m[SW_WAVES][SW_IPM_NMAX];
-    double sums[SW_IPM_NRED];
-    double maxes[SW_IPM_NMAX];
-};
-
-/* The first half of a reduction: the waves' trees into LDS and the barrier;
- * then thread 0 combines them (ipm_combine) and goes on alone. */
-__device__ __forceinline__ void ipm_publish(IpmRed& R, const double (&acc)[SW_IPM_NRED], int32_t cnt,
-                                            const double (&mx)[SW_IPM_NMAX], int32_t nmx) {
-    const int lane = lane_id(), wv = wave_id();
-#pragma unroll
-    for (int i = 0; i < SW_IPM_NRED; ++i)
-        if (i < cnt) { /* uniform */
-            const double v = wave_dettree(acc[i]);
-            if (lane == 0) R.s[wv][i] = v;
-        }
-#pragma unroll
-    for (int i = 0; i < SW_IPM_NMAX; ++i)
-        if (i < nmx) {
-            const double v = wave_max_f64(mx[i]);
-            if (lane == 0) R.m[wv][i] = v;
-        }
-    __syncthreads();
-}
-
-/* thread 0 only: the halving tree over the waves, the maxima */
-__device__ __forceinline__ void ipm_combine(IpmRed& R, int32_t cnt, int32_t nmx) {
-    for (int32_t i = 0; i < cnt; ++i) {
-        double s[SW_WAVES];
-#pragma unroll
-        for (int w = 0; w < SW_WAVES; ++w) s[w] = R.s[w][i];
-#pragma unroll
-        for (int h = SW_WAVES / 2; h >= 1; h >>= 1)
-#pragma unroll
-            for (int k = 0; k < h; ++k) s[k] = s[k] + s[k + h];
-        R.sums[i] = s[0];
-    }
-    for (int32_t i = 0; i < nmx; ++i) {
-        double m = R.m[0][i];
-#pragma unroll
-        for (int w = 1; w < SW_WAVES; ++w) m = R.m[w][i] > m ? R.m[w][i] : m;
-        R.maxes[i] = m;
-    }
-}
-
-__device__ __forceinline__ void ipm_clear(double (&acc)[SW_IPM_NRED], double (&mx)[SW_IPM_NMAX]) {
-#pragma unroll
-    for (int i = 0; i < SW_IPM_NRED; ++i) acc[i] = 0.0;
-#pragma unroll
-    for (int i = 0; i < SW_IPM_NMAX; ++i) mx[i] = kNegHuge;
-}
-
-/* acc += v[0 … cnt), mx = max(mx, w[0 … nmx)) with the arrays kept in registers */
-__device__ __forceinline__ void ipm_take(double (&acc)[SW_IPM_NRED], const double* v, int32_t cnt,
-                                         double (&mx)[SW_IPM_NMAX], const double* w, int32_t nmx) {
-#pragma unroll
-    for (int i = 0; i < SW_IPM_NRED; ++i)
-        if (i < cnt) acc[i] = acc[i] + v[i];
-#pragma unroll
-    for (int i = 0; i < SW_IPM_NMAX; ++i)
-        if (i < nmx) mx[i] = w[i] > mx[i] ? w[i] : mx[i];
-}
 
 /* levels: [count][3] = t*, Newton steps, status (SW_IPM_OK / _CAP / _BREAK) */
 __global__ __launch_bounds__(SW_BLOCK) void sw_mmf_ipm_kernel(const int64_t* __restrict__ offsets, int32_t n,
@@ -254,8 +189,6 @@ struct MmfcBufs {
     std::vector<int32_t> shifts;
 };
 
-size_t align8(size_t o) { return (o + 7) & ~(size_t)7; }
-
 int mmfc_run(sw_handle* h, const std::string& who, int32_t count, int32_t n, const int64_t* offsets,
              const int32_t* workers, const int32_t* sf, const double* coef, double* x, double* levels) {
     if (n < 1 || n > SW_IPM_MAX_TYPES || !offsets || !workers)
@@ -296,7 +229,7 @@ int mmfc_run(sw_handle* h, const std::string& who, int32_t count, int32_t n, con
      * out: x[total·n] | levels[count][3] (double) */
     const size_t C = (size_t)count, T = (size_t)total, N = (size_t)n;
     const size_t o_coef = (C + 1) * 8, o_w = o_coef + T * N * 8, o_sh = o_w + C * N * 4, o_sf = o_sh + C * 4;
-    const size_t in_bytes = align8(o_sf + T * 4);
+    const size_t in_bytes = ipm_align8(o_sf + T * 4);
     const size_t o_lv = T * N * 8, out_bytes = o_lv + C * 3 * 8;
     sw_io_bufs* b = &h->io;
     SW_HIP(h, b->in.reserve(in_bytes));

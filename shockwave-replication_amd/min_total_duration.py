@@ -10,12 +10,18 @@ feasibility solve per probe (:82-101), is replaced by ``sw_mtd_allocate``: the
 same probe sequence on the closed-form feasibility test, and the analytic
 centre of the feasible face at the found T.
 
-The kernel solves one worker type.  Several worker types whose per-job
+``sw_mtd_allocate`` solves one worker type.  Several worker types whose per-job
 throughputs are identical — what ``MinTotalDurationPolicy`` produces by copying
 the v100 throughput to every type (:25-31) — reduce to one type with Σ workers:
 the LP sees only Σ_k x[j][k], and the split x[j][k] = x_j · workers_k / Σ workers
 satisfies every type's capacity.  Throughputs that differ by type are a
-genuine LP per probe: ``NotImplementedError``.  A zero throughput raises
+genuine LP per probe: ``NotImplementedError`` unless the policy was built with
+``worker_types=True``.  Then they go to ``sw_mtd_allocate_types``
+(csrc/sw_mtd_types.h): the max-min level t* of throughput / steps over the
+types answers every probe (the LP is feasible at T exactly when T·t* ≥ 1), and
+the allocation is the analytic centre of the reference's LP at the found T;
+``last_level`` is then (T, t*, flags).  Identical throughputs still take the
+one-type path.  A zero throughput raises
 ``ValueError`` naming the job: the reference's LP is infeasible at every T
 there and its search never ends.  Remaining steps below zero are taken as
 zero: with x ≥ 0 the LP's row is the same.  The result is clipped to [0, 1]
@@ -43,11 +49,12 @@ def _flatten(d, cluster_spec):
 class MinTotalDurationPolicyWithPerf:
     """min_total_duration.py:41-106."""
 
-    def __init__(self, solver=None, native=None):
+    def __init__(self, solver=None, native=None, worker_types=False):
         self._name = "MinTotalDuration_Perf"
         self._solver = solver  # kept for the signature; the search runs on the GPU
         self._native = native
-        self.last_level = None  # (T, μ) of the last solve
+        self._worker_types = worker_types  # throughputs that differ by type: sw_mtd_allocate_types
+        self.last_level = None  # (T, μ) of the last solve; (T, t*, flags) of one over differing types
 
     @property
     def name(self):
@@ -65,9 +72,11 @@ class MinTotalDurationPolicyWithPerf:
         m, n = throughputs.shape
         job_ids, worker_types = index
         if not (throughputs == throughputs[:, :1]).all():
-            raise NotImplementedError(
-                "MinTotalDuration with throughputs that differ by worker type is not supported: "
-                "the native kernel solves one worker type (or several identical ones)")
+            if not self._worker_types:
+                raise NotImplementedError(
+                    "MinTotalDuration with throughputs that differ by worker type needs worker_types=True: "
+                    "the default kernel solves one worker type (or several identical ones)")
+            return self._allocation_over_types(throughputs, index, scale_factors, num_steps_remaining, cluster_spec)
         for i in range(m):
             if throughputs[i, 0] == 0:
                 raise ValueError(f"job {job_ids[i]} has zero throughput: no T lets it finish")
@@ -85,6 +94,22 @@ class MinTotalDurationPolicyWithPerf:
         else:
             xs = np.array([[x[i] * workers[k] / total for k in range(n)] for i in range(m)])
         xs = xs.clip(min=0.0).clip(max=1.0)
+        return {job_ids[i]: {worker_types[k]: xs[i, k] for k in range(n)} for i in range(m)}
+
+
+    def _allocation_over_types(self, throughputs, index, scale_factors, num_steps_remaining, cluster_spec):
+        m, n = throughputs.shape
+        job_ids, worker_types = index
+        workers = np.array([int(cluster_spec[wt]) for wt in worker_types], dtype=np.int32)
+        steps = np.array([max(num_steps_remaining[j], 0) for j in job_ids], dtype=np.float64)
+        for i in range(m):
+            if steps[i] > 0 and not (throughputs[i, workers > 0] > 0).any():
+                raise ValueError(f"job {job_ids[i]} has zero throughput on every worker type that has workers: "
+                                 "no T lets it finish")
+        sf = np.array([scale_factors[j] for j in job_ids], dtype=np.int32)
+        x, T, t, _, flags = self._engine().mtd_allocate_types(workers, sf, throughputs, steps)
+        self.last_level = (T, t, flags)
+        xs = np.asarray(x, dtype=np.float64).reshape(m, n).clip(min=0.0).clip(max=1.0)
         return {job_ids[i]: {worker_types[k]: xs[i, k] for k in range(n)} for i in range(m)}
 
 

@@ -321,7 +321,7 @@ EXPORTED_SYMBOLS = (
     "sw_wf_allocate", "sw_wf_allocate_batch", "sw_mtd_allocate", "sw_mtd_allocate_batch",
     "sw_mst_allocate", "sw_mst_allocate_batch", "sw_allox_assign", "sw_allox_assign_batch",
     "sw_wfh_allocate", "sw_wfh_allocate_batch", "sw_mmf_allocate_types_centred",
-    "sw_mmf_allocate_types_centred_batch",
+    "sw_mmf_allocate_types_centred_batch", "sw_mtd_allocate_types", "sw_mtd_allocate_types_batch",
 )
 
 
@@ -414,6 +414,11 @@ def load(path: str | None = None):
     lib.sw_mmf_allocate_types_centred_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), _ip,
                                                         _ip, _dp, _dp, _dp]
     lib.sw_mmf_allocate_types_centred_batch.restype = C.c_int
+    lib.sw_mtd_allocate_types.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip, _ip, _dp, _dp, _dp, _dp]
+    lib.sw_mtd_allocate_types.restype = C.c_int
+    lib.sw_mtd_allocate_types_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), _ip, _ip,
+                                                _dp, _dp, _dp, _dp]
+    lib.sw_mtd_allocate_types_batch.restype = C.c_int
     for name, (dtypes, _, _) in _ALLOC.items():
         cols = [_ip if t is np.int32 else _dp for t in dtypes]
         single, batch = getattr(lib, f"sw_{name}_allocate"), getattr(lib, f"sw_{name}_allocate_batch")
@@ -617,6 +622,63 @@ class Solver:
             "sw_mmf_allocate_types_centred_batch")
         return [(x[off[i] * n:off[i + 1] * n].reshape(-1, n).copy(), float(lvl[i, 0]), int(lvl[i, 1]))
                 for i in range(count)]
+
+    # ---- MinTotalDuration over worker types that differ (csrc/sw_mtd_types.h) ----
+    MTDT_IDLE = 1  # flags of mtd_allocate_types: no job has steps left
+    MTDT_THIN = 2  # the polytope at T is too thin to centre in (sw_mtd_types.h)
+
+    @staticmethod
+    def _mtd_types_arrays(workers, scale_factors, throughputs, steps):
+        w = np.ascontiguousarray(workers, dtype=np.int32)
+        sf = np.ascontiguousarray(scale_factors, dtype=np.int32)
+        thr = np.ascontiguousarray(throughputs, dtype=np.float64)
+        st = np.ascontiguousarray(steps, dtype=np.float64)
+        if thr.ndim != 2 or thr.shape != (len(sf), len(w)) or st.shape != (len(sf),):
+            raise ValueError("throughputs must be [num_jobs][num_types], steps [num_jobs]")
+        return w, sf, thr, st
+
+    def mtd_allocate_types(self, workers, scale_factors, throughputs, steps):
+        """The MinTotalDuration allocation over worker types whose throughputs
+        differ (sw_mtd_allocate_types): the reference's search over T on the
+        max-min level t* of throughput / steps, and the analytic centre of its
+        LP at the found T; returns (x [m, n], T, t*, Newton steps, flags)."""
+        w, sf, thr, st = self._mtd_types_arrays(workers, scale_factors, throughputs, steps)
+        x = np.zeros(thr.shape, dtype=np.float64)
+        res = np.zeros(4, dtype=np.float64)
+        self._check(self.lib.sw_mtd_allocate_types(self.h, thr.shape[0], thr.shape[1], w.ctypes.data_as(_ip),
+                                                   sf.ctypes.data_as(_ip), thr.ctypes.data_as(_dp),
+                                                   st.ctypes.data_as(_dp), x.ctypes.data_as(_dp),
+                                                   res.ctypes.data_as(_dp)),
+                    "sw_mtd_allocate_types")
+        return x, float(res[0]), float(res[1]), int(res[2]), int(res[3])
+
+    def mtd_allocate_types_batch(self, instances, offsets=None):
+        """sw_mtd_allocate_types_batch over a list of (workers, scale_factors,
+        throughputs, steps) tuples with one number of types, one kernel launch;
+        returns the list of (x [m, n], T, t*, Newton steps, flags).  offsets
+        (tests only) overrides the CSR offsets built from the instances."""
+        parts = [self._mtd_types_arrays(*inst) for inst in instances]
+        count = len(parts)
+        n = len(parts[0][0]) if parts else 1
+        if any(len(p[0]) != n for p in parts):
+            raise ValueError("every instance must have the same number of worker types")
+        off = np.zeros(count + 1, dtype=np.int64)
+        for i, p in enumerate(parts):
+            off[i + 1] = off[i] + len(p[1])
+        w = np.ascontiguousarray(np.concatenate([p[0] for p in parts]) if parts else [], dtype=np.int32)
+        sf = np.ascontiguousarray(np.concatenate([p[1] for p in parts]) if parts else [], dtype=np.int32)
+        thr = np.ascontiguousarray(np.concatenate([p[2].reshape(-1) for p in parts]) if parts else [],
+                                   dtype=np.float64)
+        st = np.ascontiguousarray(np.concatenate([p[3] for p in parts]) if parts else [], dtype=np.float64)
+        x = np.zeros(len(thr), dtype=np.float64)
+        res = np.zeros((count, 4), dtype=np.float64)
+        coff = off if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
+        self._check(self.lib.sw_mtd_allocate_types_batch(
+            self.h, count, n, coff.ctypes.data_as(C.POINTER(C.c_int64)), w.ctypes.data_as(_ip),
+            sf.ctypes.data_as(_ip), thr.ctypes.data_as(_dp), st.ctypes.data_as(_dp), x.ctypes.data_as(_dp),
+            res.ctypes.data_as(_dp)), "sw_mtd_allocate_types_batch")
+        return [(x[off[i] * n:off[i + 1] * n].reshape(-1, n).copy(), float(res[i, 0]), float(res[i, 1]),
+                 int(res[i, 2]), int(res[i, 3])) for i in range(count)]
 
     # ---- the per-job allocation policies (csrc/sw_alloc.h; _ALLOC above) ----
     @staticmethod
