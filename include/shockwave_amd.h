@@ -661,6 +661,60 @@ int sw_mtd_allocate_types_batch(sw_handle* h, int32_t count, int32_t num_types, 
                                 const double* steps, double* allocation, double* results);
 
 /*
+ * The Gavel FinishTimeFairness (Themis) baseline over worker types whose
+ * throughputs DIFFER (policies/finish_time_fairness.py:55-140 with more than
+ * one worker type; sw_ftf_allocate is the one-type program).  The reference
+ * solves, with ECOS,
+ *     minimise ρ  s.t.  elapsed_j + steps_j / Σ_k throughput_jk·x_jk ≤ ρ·expected_j,
+ *                       Σ_j scale_factor_j·x_jk ≤ workers_k,  Σ_k x_jk ≤ 1,  x ≥ 0.
+ * At a fixed ρ that is the LP Σ_k c_jk(ρ)·x_jk ≥ 1 with
+ * c_jk(ρ) = throughput_jk·(ρ·expected_j − elapsed_j)/steps_j, feasible exactly
+ * when the max-min level t*(ρ) of these rows is ≥ 1.  The call finds the root
+ * ρ* of t*(ρ) = 1 by Newton steps on t*, every level by the interior-point
+ * method of sw_mmf_allocate_types_centred, started from the least ρ the
+ * one-type program on the best full times admits (a lower bound on ρ*), and
+ * returns the ANALYTIC CENTRE of the reference's feasible set at ρ* under the
+ * linear barrier (the convention of sw_ftf_allocate; ECOS's own point on a
+ * non-trivial face is not reproduced).  A job with steps_j = 0 needs nothing:
+ * its ratio elapsed_j/expected_j bounds ρ from below and its row is x ≥ 0 only.
+ * A type with 0 workers gets shares of exactly 0.0.  Priority weights are
+ * ignored, as in the reference.
+ *   result[5] = ρ*, the level t of the last solve (1 within 1e-7 where capacity
+ * binds; where it is below 1 the ρ* returned is the solve's ρ divided by it, at
+ * which the allocation meets every row; 0.0 without a live job), Newton steps of all level solves, level solves, flags:
+ * SW_FTFT_BOX = 1 (ρ* = ρ_box = max_j (elapsed_j + steps_j / max_k
+ * throughput_jk)/expected_j, the least level the time rows admit),
+ * SW_FTFT_IDLE = 2 (no job has steps left: ρ* = max_j elapsed_j/expected_j and
+ * the allocation is the centre of the capacity and time rows alone),
+ * SW_FTFT_SAFE = 4 (a Newton step on t* overshot; the call went on with steps
+ * on 1/t*, which cannot).
+ *   Tolerances, as measured against an independent computation (a bracketing
+ * search over ρ on HiGHS's level, a null-space Newton centre;
+ * tests/test_ftf_types.py): ρ* within 1e-6 relative (measured 8.9e-8), shares
+ * within 1e-6 (measured 7.5e-8), every
+ * row of the program at the returned ρ* within 1e-9 relative.
+ *   SW_ERR_INVALID: a scale factor outside [1, 255], a negative worker count,
+ * a non-finite or negative throughput, steps or elapsed time, an expected time
+ * that is not finite and > 0, num_types outside [1, 16], num_jobs above 16384,
+ * a job with steps left and no positive throughput on a type that has workers,
+ * or whose best full time steps / max_k throughput exceeds 1e15 seconds, or a
+ * ρ_box that is not finite; the message names the job.  A step cap, a
+ * non-positive pivot or more than 32 level solves is SW_ERR_CAPACITY.
+ * num_jobs = 0 is a no-op with result (0, 0, 0, 0, 0).
+ *   The batch form takes `count` instances over one num_types in the CSR
+ * convention of sw_ftf_allocate_batch, workers [count][num_types], results
+ * [count][5]; every instance's result is bit for bit that of the single call.
+ * sw_abi_version stays 2.
+ */
+int sw_ftf_allocate_types(sw_handle* h, int32_t num_jobs, int32_t num_types, const int32_t* workers,
+                          const int32_t* scale_factors, const double* throughputs, const double* steps,
+                          const double* elapsed, const double* expected, double* allocation, double* result);
+int sw_ftf_allocate_types_batch(sw_handle* h, int32_t count, int32_t num_types, const int64_t* offsets,
+                                const int32_t* workers, const int32_t* scale_factors, const double* throughputs,
+                                const double* steps, const double* elapsed, const double* expected,
+                                double* allocation, double* results);
+
+/*
  * The Gavel max-sum-throughput baseline's allocation ("MST";
  * policies/max_sum_throughput.py:39-96, selected as max_sum_throughput_perf in
  * utils.get_policy) for one worker type.  The reference solves, with ECOS,

@@ -140,6 +140,8 @@ struct sw_handle {
     void* mmfc = nullptr;
     /* the workspace of the worker-type MinTotalDuration call (sw_mtd_types.hip) */
     void* mtdt = nullptr;
+    /* the workspace of the worker-type FinishTimeFairness call (sw_ftf_types.hip) */
+    void* ftft = nullptr;
     /* the blocks of the per-job allocation policies (sw_alloc.h) and of AlloX (sw_allox.hip) */
     sw_io_bufs io;
 };
@@ -165,6 +167,8 @@ void sw_mmf_release(sw_handle* h);
 void sw_mmfc_release(sw_handle* h);
 /* sw_mtd_types.hip: frees the worker-type MinTotalDuration call's workspace */
 void sw_mtdt_release(sw_handle* h);
+/* sw_ftf_types.hip: frees the worker-type FinishTimeFairness call's workspace */
+void sw_ftft_release(sw_handle* h);
 /* frees the shared input / output blocks */
 inline void sw_io_release(sw_handle* h) {
     h->io.in.release(); h->io.out.release(); h->io.hin.release(); h->io.hout.release();

@@ -185,23 +185,12 @@ SW_HD void sw_mtdt_glob_load(sw_ipm_glob* g, sw_mtdt_glob* q, const double* sums
     }
 }
 
-/* After phase 1 and its final pass (one thread): the search, and either the
- * thin rule (returns 0: the extrapolated point is the answer) or the switch of
- * the engine's state to phase 2 (returns 1: sw_mtdt_job_switch on every job,
- * then the Newton loop again).  g->tau receives 1/μ₂ for the jobs' pass,
- * g->rhst the amount κ-rows' slacks grow by. */
-SW_HD int sw_mtdt_glob_switch(sw_ipm_glob* g, sw_mtdt_glob* q, int32_t shift) {
-    sw_mtdt_search(q, sw_ipm_level(g, shift), 0);
-    q->phase = 1;
-    const double tc = sw_lp_scale(1.0 / q->T, shift);
-    const double ts = sw_lp_scale(q->tstar, shift);
-    const double width = ts - tc;
-    if (!(q->margin >= SW_MTDT_THIN) || !(width > 0.0)) {
-        q->flags = q->flags | SW_MTDT_THIN_FLAG;
-        return 0;
-    }
+/* The engine's state from the second path point of a level solve to its
+ * objective-free mode at the constant (normalised) level tc, width = t* − tc > 0
+ * (one thread; shared with sw_ftf_types.h).  g->tau receives 1/μ₂ for the jobs'
+ * pass (sw_mtdt_job_switch), g->rhst the amount κ-rows' slacks grow by. */
+SW_HD void sw_mtdt_glob_centre(sw_ipm_glob* g, double tc, double width) {
     const double inv = 1.0 / g->mu_end;
-    q->iters1 = g->iters;
     g->rhst = g->t > tc ? g->t - tc : 0.0;
     g->tau = inv;
     g->npairs = g->npairs - 1.0;
@@ -217,6 +206,25 @@ SW_HD int sw_mtdt_glob_switch(sw_ipm_glob* g, sw_mtdt_glob* q, int32_t shift) {
     g->done = 0;
     g->iters = 0;
     for (int32_t k = 0; k < g->na; ++k) g->sw[k] = g->sw[k] * inv;
+}
+
+/* After phase 1 and its final pass (one thread): the search, and either the
+ * thin rule (returns 0: the extrapolated point is the answer) or the switch of
+ * the engine's state to phase 2 (returns 1: sw_mtdt_job_switch on every job,
+ * then the Newton loop again).  g->tau receives 1/μ₂ for the jobs' pass,
+ * g->rhst the amount κ-rows' slacks grow by. */
+SW_HD int sw_mtdt_glob_switch(sw_ipm_glob* g, sw_mtdt_glob* q, int32_t shift) {
+    sw_mtdt_search(q, sw_ipm_level(g, shift), 0);
+    q->phase = 1;
+    const double tc = sw_lp_scale(1.0 / q->T, shift);
+    const double ts = sw_lp_scale(q->tstar, shift);
+    const double width = ts - tc;
+    if (!(q->margin >= SW_MTDT_THIN) || !(width > 0.0)) {
+        q->flags = q->flags | SW_MTDT_THIN_FLAG;
+        return 0;
+    }
+    q->iters1 = g->iters;
+    sw_mtdt_glob_centre(g, tc, width);
     return 1;
 }
 

@@ -21,7 +21,15 @@ copying the v100 throughput to every type (:35-43) — reduce to one type with
 Σ workers: the program sees only Σ_k x[j][k], and the split
 x[j][k] = x_j · workers_k / Σ workers satisfies every type's capacity.
 Throughputs that differ by type need a different solver:
-``NotImplementedError``.  A zero throughput, or a job whose expected isolated
+``NotImplementedError`` by default, and with
+``FinishTimeFairnessPolicyWithPerf(worker_types=True)`` they go to
+``sw_ftf_allocate_types``: the same program over the types as
+they are, ρ* the root of the max-min level t*(ρ) = 1 and the analytic centre of
+the feasible set at ρ*; ``last_level`` is then (ρ*, level solves).  There a zero
+throughput raises only for a job with steps left and no positive throughput on
+a type that has workers.  (A finished job whose throughputs are all zero has no
+isolated throughput either: its expected isolated time is 0/0, and the check
+of that time raises ``ValueError`` naming it, as on the default path.)  A zero throughput, or a job whose expected isolated
 time is not positive (remaining steps that grew since the previous call make
 the reference's cumulative term negative), raises ``ValueError`` naming the
 job: the reference divides by zero or builds a non-convex program there, and
@@ -65,14 +73,15 @@ def _isolated_throughputs(throughputs, index, scale_factors, cluster_spec):
 class FinishTimeFairnessPolicyWithPerf:
     """finish_time_fairness.py:55-140."""
 
-    def __init__(self, solver="ECOS", native=None):
+    def __init__(self, solver="ECOS", native=None, worker_types=False):
         self._name = "FinishTimeFairness_Perf"
         self._solver = solver  # kept for the signature; the program runs on the GPU
         self._native = native
+        self._worker_types = worker_types  # throughputs that differ by type: sw_ftf_allocate_types
         self._cumulative_isolated_time = {}
         self._isolated_throughputs_prev_iteration = {}
         self._num_steps_remaining_prev_iteration = {}
-        self.last_level = None  # (ρ*, μ) of the last solve
+        self.last_level = None  # (ρ*, μ) of the last solve; (ρ*, level solves) of one over differing types
 
     @property
     def name(self):
@@ -92,12 +101,20 @@ class FinishTimeFairnessPolicyWithPerf:
             return None
         m, n = throughputs.shape
         job_ids, worker_types = index
-        if not (throughputs == throughputs[:, :1]).all():
+        workers = [int(cluster_spec[wt]) for wt in worker_types]
+        over_types = not (throughputs == throughputs[:, :1]).all()
+        if over_types and not self._worker_types:
             raise NotImplementedError(
                 "FinishTimeFairness with throughputs that differ by worker type is not supported: "
-                "the native kernel solves one worker type (or several identical ones)")
+                "the native kernel solves one worker type (or several identical ones); "
+                "worker_types=True selects the kernel over differing types")
         for i in range(m):
-            if throughputs[i, 0] == 0:
+            if over_types:
+                live = num_steps_remaining[job_ids[i]] > 0
+                if live and not any(throughputs[i, k] > 0 for k in range(n) if workers[k] > 0):
+                    raise ValueError(f"job {job_ids[i]} has zero throughput on every worker type that has workers: "
+                                     "its finish time is undefined")
+            elif throughputs[i, 0] == 0:
                 raise ValueError(f"job {job_ids[i]} has zero throughput: its finish time is undefined")
         isolated = _isolated_throughputs(throughputs, index, scale_factors, cluster_spec)
         full_time, elapsed, expected = np.zeros(m), np.zeros(m), np.zeros(m)
@@ -111,16 +128,23 @@ class FinishTimeFairnessPolicyWithPerf:
                 ) / self._isolated_throughputs_prev_iteration[j]
             expected[i] = self._cumulative_isolated_time[j] + num_steps_remaining[j] / isolated[i]
             elapsed[i] = times_since_start[j]
-            full_time[i] = num_steps_remaining[j] / throughputs[i, 0]
+            if not over_types:
+                full_time[i] = num_steps_remaining[j] / throughputs[i, 0]
         # the state is updated before the solve can raise, in the reference's order (:128-133)
         self._num_steps_remaining_prev_iteration = copy.copy(num_steps_remaining)
         self._isolated_throughputs_prev_iteration = {job_ids[i]: isolated[i] for i in range(m)}
         for i in range(m):
             if not expected[i] > 0:
                 raise ValueError(f"job {job_ids[i]} has expected isolated time {expected[i]!r} <= 0")
-        workers = [int(cluster_spec[wt]) for wt in worker_types]
         total = sum(workers)
         sf = np.array([scale_factors[j] for j in job_ids], dtype=np.int32)
+        if over_types:
+            steps = np.array([num_steps_remaining[j] for j in job_ids], dtype=np.float64)
+            x, rho, _, _, solves, _ = self._engine().ftf_allocate_types(
+                np.array(workers, dtype=np.int32), sf, throughputs, steps, elapsed, expected)
+            self.last_level = (rho, solves)
+            xs = np.asarray(x, dtype=np.float64).reshape(m, n).clip(min=0.0).clip(max=1.0)
+            return {job_ids[i]: {worker_types[k]: xs[i, k] for k in range(n)} for i in range(m)}
         x, rho, mu = self._engine().ftf_allocate(sf, full_time, elapsed, expected, total)
         self.last_level = (rho, mu)
         x = np.asarray(x, dtype=np.float64)

@@ -322,6 +322,7 @@ EXPORTED_SYMBOLS = (
     "sw_mst_allocate", "sw_mst_allocate_batch", "sw_allox_assign", "sw_allox_assign_batch",
     "sw_wfh_allocate", "sw_wfh_allocate_batch", "sw_mmf_allocate_types_centred",
     "sw_mmf_allocate_types_centred_batch", "sw_mtd_allocate_types", "sw_mtd_allocate_types_batch",
+    "sw_ftf_allocate_types", "sw_ftf_allocate_types_batch",
 )
 
 
@@ -419,6 +420,11 @@ def load(path: str | None = None):
     lib.sw_mtd_allocate_types_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), _ip, _ip,
                                                 _dp, _dp, _dp, _dp]
     lib.sw_mtd_allocate_types_batch.restype = C.c_int
+    lib.sw_ftf_allocate_types.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp]
+    lib.sw_ftf_allocate_types.restype = C.c_int
+    lib.sw_ftf_allocate_types_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), _ip, _ip,
+                                                _dp, _dp, _dp, _dp, _dp, _dp]
+    lib.sw_ftf_allocate_types_batch.restype = C.c_int
     for name, (dtypes, _, _) in _ALLOC.items():
         cols = [_ip if t is np.int32 else _dp for t in dtypes]
         single, batch = getattr(lib, f"sw_{name}_allocate"), getattr(lib, f"sw_{name}_allocate_batch")
@@ -679,6 +685,68 @@ class Solver:
             res.ctypes.data_as(_dp)), "sw_mtd_allocate_types_batch")
         return [(x[off[i] * n:off[i + 1] * n].reshape(-1, n).copy(), float(res[i, 0]), float(res[i, 1]),
                  int(res[i, 2]), int(res[i, 3])) for i in range(count)]
+
+    # ---- FinishTimeFairness over worker types that differ (csrc/sw_ftf_types.h) ----
+    FTFT_BOX = 1   # flags of ftf_allocate_types: ρ* is the least level the time rows admit
+    FTFT_IDLE = 2  # no job has steps left
+    FTFT_SAFE = 4  # a Newton step on t* overshot, steps on 1/t* from then on
+
+    @staticmethod
+    def _ftf_types_arrays(workers, scale_factors, throughputs, steps, elapsed, expected):
+        w = np.ascontiguousarray(workers, dtype=np.int32)
+        sf = np.ascontiguousarray(scale_factors, dtype=np.int32)
+        thr = np.ascontiguousarray(throughputs, dtype=np.float64)
+        cols = [np.ascontiguousarray(v, dtype=np.float64) for v in (steps, elapsed, expected)]
+        if thr.ndim != 2 or thr.shape != (len(sf), len(w)) or any(c.shape != (len(sf),) for c in cols):
+            raise ValueError("throughputs must be [num_jobs][num_types], steps, elapsed and expected [num_jobs]")
+        return (w, sf, thr) + tuple(cols)
+
+    def ftf_allocate_types(self, workers, scale_factors, throughputs, steps, elapsed, expected):
+        """The FinishTimeFairness allocation over worker types whose throughputs
+        differ (sw_ftf_allocate_types): the root ρ* of t*(ρ) = 1, t* the max-min
+        level of throughput·(ρ·expected − elapsed)/steps, and the analytic centre
+        of the program's feasible set at ρ*; returns (x [m, n], ρ*, t*(ρ*),
+        Newton steps, level solves, flags)."""
+        w, sf, thr, st, el, ex = self._ftf_types_arrays(workers, scale_factors, throughputs, steps, elapsed, expected)
+        x = np.zeros(thr.shape, dtype=np.float64)
+        res = np.zeros(5, dtype=np.float64)
+        self._check(self.lib.sw_ftf_allocate_types(self.h, thr.shape[0], thr.shape[1], w.ctypes.data_as(_ip),
+                                                   sf.ctypes.data_as(_ip), thr.ctypes.data_as(_dp),
+                                                   st.ctypes.data_as(_dp), el.ctypes.data_as(_dp),
+                                                   ex.ctypes.data_as(_dp), x.ctypes.data_as(_dp),
+                                                   res.ctypes.data_as(_dp)),
+                    "sw_ftf_allocate_types")
+        return x, float(res[0]), float(res[1]), int(res[2]), int(res[3]), int(res[4])
+
+    def ftf_allocate_types_batch(self, instances, offsets=None):
+        """sw_ftf_allocate_types_batch over a list of (workers, scale_factors,
+        throughputs, steps, elapsed, expected) tuples with one number of types,
+        one kernel launch; returns the list of (x [m, n], ρ*, t*(ρ*), Newton
+        steps, level solves, flags).  offsets (tests only) overrides the CSR
+        offsets built from the instances."""
+        parts = [self._ftf_types_arrays(*inst) for inst in instances]
+        count = len(parts)
+        n = len(parts[0][0]) if parts else 1
+        if any(len(p[0]) != n for p in parts):
+            raise ValueError("every instance must have the same number of worker types")
+        off = np.zeros(count + 1, dtype=np.int64)
+        for i, p in enumerate(parts):
+            off[i + 1] = off[i] + len(p[1])
+
+        def cat(c, dtype):
+            return np.ascontiguousarray(np.concatenate([p[c].reshape(-1) for p in parts]) if parts else [], dtype=dtype)
+
+        w, sf, thr = cat(0, np.int32), cat(1, np.int32), cat(2, np.float64)
+        st, el, ex = cat(3, np.float64), cat(4, np.float64), cat(5, np.float64)
+        x = np.zeros(len(thr), dtype=np.float64)
+        res = np.zeros((count, 5), dtype=np.float64)
+        coff = off if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
+        self._check(self.lib.sw_ftf_allocate_types_batch(
+            self.h, count, n, coff.ctypes.data_as(C.POINTER(C.c_int64)), w.ctypes.data_as(_ip),
+            sf.ctypes.data_as(_ip), thr.ctypes.data_as(_dp), st.ctypes.data_as(_dp), el.ctypes.data_as(_dp),
+            ex.ctypes.data_as(_dp), x.ctypes.data_as(_dp), res.ctypes.data_as(_dp)), "sw_ftf_allocate_types_batch")
+        return [(x[off[i] * n:off[i + 1] * n].reshape(-1, n).copy(), float(res[i, 0]), float(res[i, 1]),
+                 int(res[i, 2]), int(res[i, 3]), int(res[i, 4])) for i in range(count)]
 
     # ---- the per-job allocation policies (csrc/sw_alloc.h; _ALLOC above) ----
     @staticmethod
