@@ -112,11 +112,29 @@ static __device__ __forceinline__ int p2x_class(const sw_p2x_lds* L, int32_t w) 
     return k;
 }
 
+/* A candidate (distance cb through source ct) per half-wave into the better of
+ * the two in both halves; the upper half (lanes 32–63) wins only when strictly
+ * smaller.  v_permlane32_swap of a register with itself leaves the lower
+ * half's value in both halves of [0] and the upper half's in both of [1]. */
+static __device__ __forceinline__ void p2x_halves_min(double& cb, int& ct) {
+    const uint64_t cu = sw_bits(cb);
+    const auto slo = __builtin_amdgcn_permlane32_swap((uint32_t)cu, (uint32_t)cu, false, false);
+    const auto shi = __builtin_amdgcn_permlane32_swap((uint32_t)(cu >> 32), (uint32_t)(cu >> 32), false, false);
+    const auto sct = __builtin_amdgcn_permlane32_swap((uint32_t)ct, (uint32_t)ct, false, false);
+    const double cl = __longlong_as_double((long long)(((uint64_t)shi[0] << 32) | slo[0]));
+    const double ch = __longlong_as_double((long long)(((uint64_t)shi[1] << 32) | slo[1]));
+    const bool up = ch < cl;
+    cb = up ? ch : cl;
+    ct = (int)(up ? sct[1] : sct[0]);
+}
+
 /* Bellman–Ford of oracle/p2x_twin.c find_cycle, block-wide: each sweep,
  * every wave relaxes ⌈T / 8⌉ consecutive source rounds (lane u = target
  * round u: the smallest d[t] + W[t][u] of its rows and their first t, read
- * against the distances in LDS), then wave 0 combines the eight in round
- * order (strict <: the sequential scan's answer), adds V (a wave-uniform
+ * against the distances in LDS; up to T = 32 the rows are split between the
+ * wave's halves, target round = lane & 31, and p2x_halves_min joins them),
+ * then wave 0 combines the eight in round order (strict <: the sequential
+ * scan's answer; up to T = 32 four per half-wave), adds V (a wave-uniform
  * scalar; its minimum by a DPP reduction), publishes the new distances and,
  * after the odd sweeps and the last, checks the predecessor graph for a
  * cycle by pointer doubling: 2^⌈log2(T + 1)⌉ ≥ T + 1 steps from a vertex are
@@ -158,10 +176,35 @@ static __device__ __forceinline__ void p2x_find_cycle(sw_p2x_lds* L, const doubl
         acc[7] += 1;
 #endif
         BF_STAMP(10);
-        {
-            /* W[t][t] and missing edges are SW_P2X_NONE; an entry at or above
-             * it is no edge (the twin's !(w < SW_P2X_NONE)), whatever the
-             * distances: they can lie below −SW_P2X_NONE */
+        /* W[t][t] and missing edges are SW_P2X_NONE; an entry at or above
+         * it is no edge (the twin's !(w < SW_P2X_NONE)), whatever the
+         * distances: they can lie below −SW_P2X_NONE */
+        if (T <= 32) {
+            /* two rows per wave instruction: the wave's nq ≤ 4 rows are split
+             * between its half-waves, the first ⌈nq / 2⌉ ≤ 2 to lanes 0–31 and
+             * the rest to lanes 32–63 (target round = lane & 31), every load
+             * goes out before the first compare, and the halves are combined
+             * once: the upper half holds the later rows and wins only when
+             * strictly smaller — the sequential strict-< scan's answer */
+            const int hf = lane >> 5, l5 = lane & 31;
+            const int ul = l5 < T ? l5 : 0;
+            const int nh = (nq + 1) >> 1;
+            const int t0 = wv * nq, ta = t0 + hf * nh, tb = ta + 1;
+            const int te = min(T, hf ? t0 + nq : t0 + nh);
+            const int ra = min(ta, T - 1), rb = min(tb, T - 1); /* rows read: in range always */
+            const double wa = W[ra * T + ul], wb = W[rb * T + ul];
+            const double da = L->bd[ra], db = L->bd[rb];
+            const double va = da + wa, vb = db + wb;
+            const bool takea = ta < te && wa < SW_P2X_NONE && va < SW_P2X_NONE;
+            double cb = takea ? va : SW_P2X_NONE;
+            int ct = takea ? ta : 0;
+            const bool takeb = tb < te && wb < SW_P2X_NONE && vb < cb;
+            cb = takeb ? vb : cb;
+            ct = takeb ? tb : ct;
+            p2x_halves_min(cb, ct);
+            L->pv[wv][lane] = cb;
+            L->pt[wv][lane] = (int8_t)ct;
+        } else {
             const int ul = act ? lane : 0;
             const int t0 = wv * nq, t1 = min(T, t0 + nq);
             double cb = SW_P2X_NONE;
@@ -186,14 +229,34 @@ static __device__ __forceinline__ void p2x_find_cycle(sw_p2x_lds* L, const doubl
             int pr = act ? L->bp[lane] : -1;
             const double dV = L->bd[T];
             int prV = L->bp[T];
-            double cb = L->pv[0][lane];
-            int ct = L->pt[0][lane];
+            double cb;
+            int ct;
+            if (T <= 32) {
+                /* the same split for the eight partials: waves 0–3's in lanes
+                 * 0–31, waves 4–7's in lanes 32–63 (a wave past the last row
+                 * left SW_P2X_NONE), the halves combined once */
+                static_assert(SW_WAVES == 8, "four partials per half-wave");
+                const int q0 = (lane >> 5) * 4, l5 = lane & 31;
+                cb = L->pv[q0][l5];
+                ct = L->pt[q0][l5];
 #pragma unroll
-            for (int q = 1; q < SW_WAVES; ++q) {
-                const double v = L->pv[q][lane];
-                const bool take = q * nq < T && v < cb;
-                cb = take ? v : cb;
-                ct = take ? L->pt[q][lane] : ct;
+                for (int q = 1; q < 4; ++q) {
+                    const double v = L->pv[q0 + q][l5];
+                    const bool take = v < cb;
+                    cb = take ? v : cb;
+                    ct = take ? L->pt[q0 + q][l5] : ct;
+                }
+                p2x_halves_min(cb, ct);
+            } else {
+                cb = L->pv[0][lane];
+                ct = L->pt[0][lane];
+#pragma unroll
+                for (int q = 1; q < SW_WAVES; ++q) {
+                    const double v = L->pv[q][lane];
+                    const bool take = q * nq < T && v < cb;
+                    cb = take ? v : cb;
+                    ct = take ? L->pt[q][lane] : ct;
+                }
             }
             double best = d;
             int bpr = pr;
