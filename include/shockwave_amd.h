@@ -715,6 +715,65 @@ int sw_ftf_allocate_types_batch(sw_handle* h, int32_t count, int32_t num_types, 
                                 double* allocation, double* results);
 
 /*
+ * The Gavel water-filling MaxMinFairness baseline over worker types whose
+ * throughputs DIFFER (policies/max_min_fairness_water_filling.py:303-409, the
+ * WithPerf class without entities; sw_wf_allocate is the one-type program).
+ * With coefficients[j][k] = throughput_jk / proportional_j · (1 / weight_j) ·
+ * scale_factor_j (computed by the caller) and val_j = Σ_k coefficients_jk·x_jk,
+ * the reference raises every unfrozen job by a common amount per stage (ECOS),
+ * finds the jobs that can rise no further (a GLPK MILP) and freezes them.  The
+ * fixed point is the LEXICOGRAPHIC MAX-MIN vector of val_j over
+ *     Σ_j scale_factor_j·x_jk ≤ workers_k,  Σ_k x_jk ≤ 1,  x ≥ 0,
+ * which is unique.  The call runs the stages in one kernel: every stage is a
+ * level solve of the interior-point method of sw_mmf_allocate_types_centred on
+ * the rows t ≤ val_j (unfrozen) and levels_j ≤ val_j (frozen), and the
+ * bottlenecks of a stage are read off its strictly complementary end point
+ * (slack over dual of the job's row, both extrapolated to the end of the path,
+ * against a measured threshold; no MILP).
+ * allocation receives the analytic centre of the LAST stage's optimal face, as
+ * the reference returns; levels receives num_jobs doubles, the level each job
+ * froze at.  Frozen rows are eased by a part in 2^30 (the later stages need
+ * the room; csrc/sw_wf_types.h), the levels returned likewise, and what that
+ * lifts the later levels by is taken off them again.  A stage whose solve
+ * breaks down is solved again, up to twice, with the ease and the path's end
+ * point eight times larger each time.  A type with 0 workers gets shares of
+ * exactly 0.0.
+ *   result[4] = the last stage's level, Newton steps of all stages, stages,
+ * flags: SW_WFT_ONE = 1 (a single stage froze every job: the allocation is that
+ * of sw_mmf_allocate_types_centred on the same rows, bit for bit), SW_WFT_NEAR
+ * = 2 (a job's statistic came within a factor 10 of the threshold: a job may
+ * have frozen a stage early or late), SW_WFT_COARSE = 4 (a stage was solved
+ * again after a breakdown: the levels are eased by up to a part in 2^24).
+ *   Tolerances, as measured against an independent computation (the stage loop
+ * on HiGHS with one LP per unfrozen job, a null-space Newton centre;
+ * tests/test_wf_types.py) on instances of 2 to 24 jobs and 2 to 4 types, 1,950
+ * of seven seeds: the same jobs frozen in the same stages on all, no call
+ * refused, levels within 1e-6 relative (9.7e-8 on all but three instances,
+ * 8.6e-7 the worst: the ease, amplified, where the lift's dual is not unique),
+ * every row of the program at the returned levels within 1e-9 relative.
+ * BEYOND 24 JOBS NOTHING IS VALIDATED AGAINST A REFERENCE: the call accepts
+ * 16,384 jobs and the kernel equals its CPU twin there, but the statistic's
+ * threshold is measured at up to 24 jobs and a bottleneck's dual falls with the
+ * number of bottlenecks; watch SW_WFT_NEAR.
+ *   SW_ERR_INVALID: a scale factor outside [1, 255], a negative worker count,
+ * a non-finite or negative coefficient, num_types outside [1, 16], num_jobs
+ * above 16384, or a job with no positive coefficient on a type that has
+ * workers (its normalised throughput is undefined); the message names the job.
+ * A step cap, a non-positive pivot or a stage that freezes no job is
+ * SW_ERR_CAPACITY.  num_jobs = 0 is a no-op with result (0, 0, 0, 0).
+ *   The batch form takes `count` instances over one num_types in the CSR
+ * convention of sw_ftf_allocate_batch, workers [count][num_types], levels over
+ * all jobs, results [count][4]; every instance's result is bit for bit that of
+ * the single call.  sw_abi_version stays 2.
+ */
+int sw_wf_allocate_types(sw_handle* h, int32_t num_jobs, int32_t num_types, const int32_t* workers,
+                         const int32_t* scale_factors, const double* coefficients, double* allocation,
+                         double* levels, double* result);
+int sw_wf_allocate_types_batch(sw_handle* h, int32_t count, int32_t num_types, const int64_t* offsets,
+                               const int32_t* workers, const int32_t* scale_factors, const double* coefficients,
+                               double* allocation, double* levels, double* results);
+
+/*
  * The Gavel max-sum-throughput baseline's allocation ("MST";
  * policies/max_sum_throughput.py:39-96, selected as max_sum_throughput_perf in
  * utils.get_policy) for one worker type.  The reference solves, with ECOS,

@@ -214,6 +214,7 @@ void sw_destroy(sw_handle* h) {
     sw_mmfc_release(h);
     sw_mtdt_release(h);
     sw_ftft_release(h);
+    sw_wft_release(h);
     sw_io_release(h);
     h->d_in.release(); h->d_res.release();
     h->d_ws_u8.release(); h->d_ws_u64.release(); h->d_ws_sort.release();

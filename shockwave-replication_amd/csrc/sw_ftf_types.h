@@ -317,6 +317,7 @@ SW_HD void sw_ftft_job_load(const sw_ipm_glob* g, const sw_ftft_glob* q, sw_ipm_
     }
     SW_IPM_Q(J, SW_IPM_HASV) = mx > 0.0 ? 1.0 : 0.0;
     SW_IPM_Q(J, SW_IPM_KAP) = live ? 1.0 : 0.0;
+    SW_IPM_Q(J, SW_IPM_BET) = 0.0;
     {
         const int32_t k = sw_lp_shift(mx);
         SW_IPM_Q(J, SW_IPM_RSC) = mx > 0.0 && k < 0 ? sw_lp_scale(1.0, k) : 1.0;

@@ -142,6 +142,8 @@ struct sw_handle {
     void* mtdt = nullptr;
     /* the workspace of the worker-type FinishTimeFairness call (sw_ftf_types.hip) */
     void* ftft = nullptr;
+    /* the workspace of the worker-type water-filling call (sw_wf_types.hip) */
+    void* wft = nullptr;
     /* the blocks of the per-job allocation policies (sw_alloc.h) and of AlloX (sw_allox.hip) */
     sw_io_bufs io;
 };
@@ -169,6 +171,8 @@ void sw_mmfc_release(sw_handle* h);
 void sw_mtdt_release(sw_handle* h);
 /* sw_ftf_types.hip: frees the worker-type FinishTimeFairness call's workspace */
 void sw_ftft_release(sw_handle* h);
+/* sw_wf_types.hip: frees the worker-type water-filling call's workspace */
+void sw_wft_release(sw_handle* h);
 /* frees the shared input / output blocks */
 inline void sw_io_release(sw_handle* h) {
     h->io.in.release(); h->io.out.release(); h->io.hin.release(); h->io.hout.release();

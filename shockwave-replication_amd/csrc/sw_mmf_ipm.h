@@ -113,6 +113,7 @@ typedef struct {
     double S[SW_IPM_MAX_TYPES * SW_IPM_MAX_TYPES]; /* lower triangle: S, then L and D in place */
     double q[SW_IPM_MAX_TYPES], r[SW_IPM_MAX_TYPES], a[SW_IPM_MAX_TYPES], b[SW_IPM_MAX_TYPES];
     double dyc[SW_IPM_MAX_TYPES], tau, rhst;
+    double mu1; /* μ₁ of the normalised program at level 1: SW_IPM_MU_1; sw_wf_types.h raises it for a stage it solves again */
 } sw_ipm_glob;
 
 /* The per-job workspace, structure of arrays: field f of job j at
@@ -127,10 +128,23 @@ typedef struct {
  * multiplied before they are held against SW_IPM_RES: 1.0 here, where every
  * coefficient is below 2; 1/(the row's largest coefficient) where rows are
  * larger (sw_mtd_types.h), whose residuals' rounding grows with it.  With has_t = 0, g->t is a constant of
- * the rows: 0.0 here, the fixed level of sw_mtd_types.h's second phase. */
+ * the rows: 0.0 here, the fixed level of sw_mtd_types.h's second phase.
+ *   SW_IPM_BET is β_j, the constant of the job's value row
+ * (κ_j·t + β_j ≤ Σ_k c·x): 0.0 for every program but the staged one of
+ * sw_wf_types.h, so that each operation with it is exact and those programs'
+ * bits are what they were before β existed; there a job frozen at the level
+ * F_j has κ = 0 and β = F_j.  It enters the start (sw_ipm_job_start2) and the
+ * primal residual (sw_ipm_rpv) and nothing else: a constant drops out of every
+ * difference.
+ *   The start x = θ need not meet such a row, so its slack starts at
+ * max(Σ c·θ − κ·t − β, ½·Σ c·θ) and the row's residual is worked off by the
+ * steps like any other; with β = 0 the first is never the smaller
+ * (t ≤ ½·Σ c·θ), so nothing changes there.
+ *   SW_IPM_SU1 and SW_IPM_U1 keep the value row's dual and slack at the first
+ * path point, as X1 keeps the shares: sw_wf_types.h extrapolates both. */
 enum { SW_IPM_U, SW_IPM_SU, SW_IPM_V, SW_IPM_SV, SW_IPM_DU, SW_IPM_DSU, SW_IPM_DV, SW_IPM_DSV,
        SW_IPM_DDU, SW_IPM_DDV, SW_IPM_HU, SW_IPM_HV, SW_IPM_RHOV, SW_IPM_RHOT, SW_IPM_DET, SW_IPM_HASV,
-       SW_IPM_KAP, SW_IPM_RSC, SW_IPM_NSCAL };
+       SW_IPM_KAP, SW_IPM_RSC, SW_IPM_BET, SW_IPM_SU1, SW_IPM_U1, SW_IPM_NSCAL };
 #define SW_IPM_FIELDS(n) (8 * (n) + SW_IPM_NSCAL)
 
 typedef struct {
@@ -163,6 +177,7 @@ SW_HD void sw_ipm_setup(sw_ipm_glob* g, int32_t m, int32_t n, const int32_t* wor
     g->done = 0;
     g->stage = 0;
     g->save = 0;
+    g->mu1 = SW_IPM_MU_1;
     for (int32_t k = 0; k < n; ++k)
         if (workers[k] > 0) {
             g->act[g->na] = k;
@@ -191,6 +206,7 @@ SW_HD void sw_ipm_job_load(const sw_ipm_glob* g, sw_ipm_job* J, const double* co
     SW_IPM_Q(J, SW_IPM_HASV) = mx > 0.0 ? 1.0 : 0.0;
     SW_IPM_Q(J, SW_IPM_KAP) = 1.0;
     SW_IPM_Q(J, SW_IPM_RSC) = 1.0;
+    SW_IPM_Q(J, SW_IPM_BET) = 0.0;
     sums[0] = J->sf;
     sums[1] = mx > 0.0 ? 1.0 : 0.0;
     maxes[0] = -mx;
@@ -201,7 +217,7 @@ SW_HD void sw_ipm_glob_load(sw_ipm_glob* g, const double* sums, const double* ma
     g->sfsum = sums[0];
     g->nv = sums[1];
     g->has_t = -maxes[0] > 0.0 ? 1 : 0;
-    g->mu_end = g->has_t ? SW_IPM_MU_1 : 1.0;
+    g->mu_end = g->has_t ? g->mu1 : 1.0;
     g->scale = 1.0;
     g->npairs = (double)g->m * (double)g->na + g->nv + (double)g->m + (double)g->na + (double)g->has_t;
     for (int32_t k = 0; k < g->na; ++k)
@@ -242,7 +258,11 @@ SW_HD void sw_ipm_job_start2(const sw_ipm_glob* g, sw_ipm_job* J) {
         mx = sw_max(mx, SW_IPM_C(J, k));
     }
     const double sv = 1.0 + mx * su;
-    SW_IPM_Q(J, SW_IPM_U) = hasv ? SW_IPM_Q(J, SW_IPM_U) - SW_IPM_Q(J, SW_IPM_KAP) * g->t : 0.0;
+    {
+        const double val = SW_IPM_Q(J, SW_IPM_U);
+        const double u = val - SW_IPM_Q(J, SW_IPM_KAP) * g->t - SW_IPM_Q(J, SW_IPM_BET);
+        SW_IPM_Q(J, SW_IPM_U) = hasv ? sw_max(u, 0.5 * val) : 0.0;
+    }
     SW_IPM_Q(J, SW_IPM_SU) = su;
     SW_IPM_Q(J, SW_IPM_V) = 1.0 - sx;
     SW_IPM_Q(J, SW_IPM_SV) = sv;
@@ -254,7 +274,7 @@ SW_HD double sw_ipm_rpv(const sw_ipm_glob* g, const sw_ipm_job* J) {
     double val = 0.0;
     if (SW_IPM_Q(J, SW_IPM_HASV) == 0.0) return 0.0;
     for (int32_t k = 0; k < J->na; ++k) val = val + SW_IPM_C(J, k) * SW_IPM_X(J, k);
-    return val - SW_IPM_Q(J, SW_IPM_KAP) * g->t - SW_IPM_Q(J, SW_IPM_U);
+    return val - SW_IPM_Q(J, SW_IPM_KAP) * g->t - SW_IPM_Q(J, SW_IPM_BET) - SW_IPM_Q(J, SW_IPM_U);
 }
 SW_HD double sw_ipm_rpt(const sw_ipm_job* J) {
     double sx = 0.0;
@@ -322,7 +342,7 @@ SW_HD void sw_ipm_glob_resid(sw_ipm_glob* g, const double* sums, const double* m
      * is still far from its first point, μ₁ follows min(1, t); then it is kept. */
     if (g->has_t && g->stage == 0 && g->mu > SW_IPM_FAR * g->mu_end) {
         g->scale = sw_min(1.0, g->t);
-        g->mu_end = SW_IPM_MU_1 * g->scale;
+        g->mu_end = g->mu1 * g->scale;
     }
     if (dev <= SW_IPM_DEV && pinf <= SW_IPM_RES && dinf <= SW_IPM_RES * g->scale) {
         if (!g->has_t || g->stage == 1) {
@@ -333,7 +353,7 @@ SW_HD void sw_ipm_glob_resid(sw_ipm_glob* g, const double* sums, const double* m
         g->stage = 1;
         g->save = 1;
         g->t1 = g->t;
-        g->mu_end = SW_IPM_MU_1 * g->scale / SW_IPM_MU_RATIO;
+        g->mu_end = g->mu1 * g->scale / SW_IPM_MU_RATIO;
     }
     if (g->iters >= SW_IPM_MAX_ITERS) {
         g->status = SW_IPM_CAP;
@@ -389,6 +409,10 @@ SW_HD void sw_ipm_job_prep(const sw_ipm_glob* g, sw_ipm_job* J) {
     }
     if (hasv) {
         const double u = SW_IPM_Q(J, SW_IPM_U), su = SW_IPM_Q(J, SW_IPM_SU), hu = tg / su - u;
+        if (g->save) {
+            SW_IPM_Q(J, SW_IPM_SU1) = su;
+            SW_IPM_Q(J, SW_IPM_U1) = u;
+        }
         SW_IPM_Q(J, SW_IPM_DDU) = u / su;
         SW_IPM_Q(J, SW_IPM_HU) = hu;
         /* row: κ·t − Σ c·x + u = 0, so r_p = Σ c·x − κ·t − u */

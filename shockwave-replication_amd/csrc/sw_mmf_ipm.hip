@@ -12,7 +12,7 @@
  * chunk [L·q, (L+1)·q) of the deterministic sum (q = ⌈m/512⌉), so the CPU twin
  * (tests/twins/mmfc_twin.c) returns the same bits.
  *
- *   per job    x, s, the slacks, their steps and scalings: 8·na + 18 doubles in
+ *   per job    x, s, the slacks, their steps and scalings: 8·na + 21 doubles in
  *              a workspace on the handle (HBM, L2-resident at these sizes),
  *              structure of arrays
  *   LDS        sw_ipm_glob (t, the capacity slacks, the reduced system: 4 KB)

@@ -13,7 +13,7 @@
  * [L·q, (L+1)·q) of the deterministic sum (q = ⌈m/512⌉), so the CPU twin
  * (tests/twins/mtdt_twin.c) returns the same bits.
  *
- *   per job    the engine's workspace, 8·na + 18 doubles on the handle (HBM,
+ *   per job    the engine's workspace, 8·na + 21 doubles on the handle (HBM,
  *              L2-resident at these sizes), structure of arrays
  *   LDS        sw_ipm_glob (4 KB), sw_mtdt_glob (T, t*, flags) and the
  *              reduction scratch (sw_mmf_ipm_dev.h)

@@ -12,7 +12,7 @@ GLPK MILP per stage) is replaced by ``sw_wf_allocate``, which returns the
 loop's fixed point x_j = min(1, L*/c_j), c_j = scale factor / priority weight,
 in one kernel.
 
-The kernel solves one worker type.  Several worker types whose per-job
+``sw_wf_allocate`` solves one worker type.  Several worker types whose per-job
 throughputs are identical — always the case for
 ``MaxMinFairnessWaterFillingPolicy``, which replaces every throughput by 1.0
 (:437-441) — reduce to one type with Σ workers: the proportional throughput of
@@ -31,17 +31,32 @@ Not built here:
     (naming those classes); ``entity_weights`` and ``entity_to_job_mapping``
     are accepted and, as in the reference without reweighting (:30-32), unused.
     The reference scheduler never passes entities (scheduler.py:2433-2436);
-  * throughputs that differ by worker type: ``NotImplementedError`` (the staged
-    LPs would have to run on the GPU simplex, and the bottleneck test's parity
-    cannot be pinned without the reference's solvers);
+  * throughputs that differ by worker type raise ``NotImplementedError`` unless
+    the WithPerf policy is built with ``worker_types=True``.  Then they go to
+    ``sw_wf_allocate_types``: the stage loop in one kernel on the
+    coefficients c_jk = thr_jk / prop_j · (1/w_j)·sf_j, every stage a level solve
+    of the interior-point engine, the bottlenecks read off its end point
+    instead of the MILP; the shares are the centre of the last stage's optimal
+    face, as the reference's last ECOS point is.  ``last_level`` is then (last
+    level, stages), ``last_flags`` the call's flags, and a flagged result
+    (SW_WFT_NEAR, SW_WFT_COARSE) raises ``WaterFillingStageWarning``.  Identical throughputs still go to ``sw_wf_allocate``;
+  * entities over worker types that differ, warm starts between the stages;
   * ``MaxMinFairnessWaterFillingPolicyWithPacking`` (:559-691).
 A priority weight ≤ 0 (the reference never raises such a job, :336-345) or a
 zero throughput (its proportional throughput divides by zero, :127-129) raises
 ``ValueError`` naming the job.
 """
+import warnings
+
 import numpy as np
 
 import sw_native
+
+
+class WaterFillingStageWarning(UserWarning):
+    """sw_wf_allocate_types flagged its own result: a bottleneck statistic near
+    its threshold (a job may have frozen a stage late or early) or a stage solved
+    again at a coarser path point (levels eased by more than a part in 2^30)."""
 
 
 def _flatten(d, cluster_spec):
@@ -76,12 +91,14 @@ def _check_reweighting(priority_reweighting_policies):
 class MaxMinFairnessWaterFillingPolicyWithPerf:
     """max_min_fairness_water_filling.py:471-556."""
 
-    def __init__(self, priority_reweighting_policies=None, native=None):
+    def __init__(self, priority_reweighting_policies=None, native=None, worker_types=False):
         _check_reweighting(priority_reweighting_policies)
         self._name = "MaxMinFairnessWaterFilling_Perf"
         self._priority_reweighting_policies = priority_reweighting_policies
         self._native = native
-        self.last_level = None  # (L*, Σ sf_j·x_j) of the last solve
+        self._worker_types = worker_types  # throughputs that differ by type: sw_wf_allocate_types
+        self.last_level = None  # (L*, Σ sf_j·x_j) of the last solve; (last level, stages) over differing types
+        self.last_flags = 0  # the flags of the last sw_wf_allocate_types call (SW_WFT_NEAR, SW_WFT_COARSE)
 
     @property
     def name(self):
@@ -101,9 +118,13 @@ class MaxMinFairnessWaterFillingPolicyWithPerf:
         m, n = throughputs.shape
         job_ids, worker_types = index
         if not (throughputs == throughputs[:, :1]).all():
-            raise NotImplementedError(
-                "water filling with throughputs that differ by worker type is not supported: "
-                "the native kernel solves one worker type (or several identical ones)")
+            if not self._worker_types:
+                raise NotImplementedError(
+                    "water filling with throughputs that differ by worker type is not supported: "
+                    "the native kernel solves one worker type (or several identical ones)")
+            return self._allocate_types(throughputs, job_ids, worker_types, scale_factors,
+                                        unflattened_priority_weights, cluster_spec, verbose,
+                                        return_effective_throughputs)
         for i, j in enumerate(job_ids):
             if throughputs[i, 0] == 0:
                 raise ValueError(f"job {j} has zero throughput: its normalised throughput is undefined")
@@ -129,6 +150,41 @@ class MaxMinFairnessWaterFillingPolicyWithPerf:
             return np.sum(xs, axis=1), job_ids
         xs = xs.clip(min=0.0).clip(max=1.0)
         return {job_ids[i]: {worker_types[k]: xs[i, k] for k in range(n)} for i in range(m)}
+
+
+    def _allocate_types(self, throughputs, job_ids, worker_types, scale_factors, priority_weights, cluster_spec,
+                        verbose, return_effective_throughputs):
+        """:303-409 over throughputs that differ by worker type."""
+        m, n = throughputs.shape
+        workers = np.array([int(cluster_spec[wt]) for wt in worker_types], dtype=np.int32)
+        for i, j in enumerate(job_ids):
+            if not (throughputs[i, workers > 0] > 0).any():
+                raise ValueError(f"job {j} has no throughput on a worker type that has workers: "
+                                 "its normalised throughput is undefined")
+            if not priority_weights[j] > 0:
+                raise ValueError(f"job {j} has priority weight {priority_weights[j]!r} <= 0")
+        prop = _proportional_throughputs(throughputs, worker_types, cluster_spec)
+        sf = np.array([scale_factors[j] for j in job_ids], dtype=np.int32)
+        # mult_j = (1 / w_j) · sf_j in the reference's float operations (:336-345, :146-148)
+        mult = np.array([(1.0 / priority_weights[j]) * scale_factors[j] for j in job_ids], dtype=np.float64)
+        coef = throughputs / prop[:, None] * mult[:, None]
+        x, levels, level, steps, stages, flags = self._engine().wf_allocate_types(workers, sf, coef)
+        self.last_level = (level, stages)
+        self.last_flags = flags
+        if flags & (sw_native.Solver.WFT_NEAR | sw_native.Solver.WFT_COARSE):
+            warnings.warn("sw_wf_allocate_types: " + " and ".join(
+                t for b, t in ((sw_native.Solver.WFT_NEAR, "a job's bottleneck statistic came within a factor 10 "
+                                "of its threshold (validated up to 24 jobs; a stage may be spurious)"),
+                               (sw_native.Solver.WFT_COARSE, "a stage's solve broke down and was done again at a "
+                                "coarser path point and ease")) if flags & b), WaterFillingStageWarning, stacklevel=3)
+        x = np.asarray(x, dtype=np.float64)
+        if verbose:
+            print("Normalized effective throughputs:", np.sum(throughputs * x, axis=1) / prop)
+            print("Last water level:", level, "stages:", stages)
+        if return_effective_throughputs:
+            return np.sum(np.multiply(throughputs, x), axis=1) / prop, job_ids
+        x = x.clip(min=0.0).clip(max=1.0)
+        return {job_ids[i]: {worker_types[k]: x[i, k] for k in range(n)} for i in range(m)}
 
 
 class MaxMinFairnessWaterFillingPolicy:

@@ -322,7 +322,7 @@ EXPORTED_SYMBOLS = (
     "sw_mst_allocate", "sw_mst_allocate_batch", "sw_allox_assign", "sw_allox_assign_batch",
     "sw_wfh_allocate", "sw_wfh_allocate_batch", "sw_mmf_allocate_types_centred",
     "sw_mmf_allocate_types_centred_batch", "sw_mtd_allocate_types", "sw_mtd_allocate_types_batch",
-    "sw_ftf_allocate_types", "sw_ftf_allocate_types_batch",
+    "sw_ftf_allocate_types", "sw_ftf_allocate_types_batch", "sw_wf_allocate_types", "sw_wf_allocate_types_batch",
 )
 
 
@@ -425,6 +425,11 @@ def load(path: str | None = None):
     lib.sw_ftf_allocate_types_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), _ip, _ip,
                                                 _dp, _dp, _dp, _dp, _dp, _dp]
     lib.sw_ftf_allocate_types_batch.restype = C.c_int
+    lib.sw_wf_allocate_types.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip, _ip, _dp, _dp, _dp, _dp]
+    lib.sw_wf_allocate_types.restype = C.c_int
+    lib.sw_wf_allocate_types_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), _ip, _ip,
+                                               _dp, _dp, _dp, _dp]
+    lib.sw_wf_allocate_types_batch.restype = C.c_int
     for name, (dtypes, _, _) in _ALLOC.items():
         cols = [_ip if t is np.int32 else _dp for t in dtypes]
         single, batch = getattr(lib, f"sw_{name}_allocate"), getattr(lib, f"sw_{name}_allocate_batch")
@@ -747,6 +752,66 @@ class Solver:
             ex.ctypes.data_as(_dp), x.ctypes.data_as(_dp), res.ctypes.data_as(_dp)), "sw_ftf_allocate_types_batch")
         return [(x[off[i] * n:off[i + 1] * n].reshape(-1, n).copy(), float(res[i, 0]), float(res[i, 1]),
                  int(res[i, 2]), int(res[i, 3]), int(res[i, 4])) for i in range(count)]
+
+    WFT_ONE = 1   # flags of wf_allocate_types: a single stage froze every job
+    WFT_NEAR = 2  # a job's statistic came within a factor 10 of the bottleneck threshold
+    WFT_COARSE = 4  # a stage's solve broke down and was done again at a larger ease and path point
+
+    @staticmethod
+    def _wf_types_arrays(workers, scale_factors, coefficients):
+        w = np.ascontiguousarray(workers, dtype=np.int32)
+        sf = np.ascontiguousarray(scale_factors, dtype=np.int32)
+        c = np.ascontiguousarray(coefficients, dtype=np.float64)
+        if c.ndim != 2 or c.shape != (len(sf), len(w)):
+            raise ValueError("coefficients must be [num_jobs][num_types]")
+        return w, sf, c
+
+    def wf_allocate_types(self, workers, scale_factors, coefficients):
+        """The water-filling MaxMinFairness allocation over worker types whose
+        throughputs differ (sw_wf_allocate_types): the lexicographic max-min
+        vector of Σ_k coefficients·x by stages and the analytic centre of the
+        last stage's optimal face; returns (x [m, n], levels [m], last level,
+        Newton steps, stages, flags)."""
+        w, sf, c = self._wf_types_arrays(workers, scale_factors, coefficients)
+        x = np.zeros(c.shape, dtype=np.float64)
+        lv = np.zeros(c.shape[0], dtype=np.float64)
+        res = np.zeros(4, dtype=np.float64)
+        self._check(self.lib.sw_wf_allocate_types(self.h, c.shape[0], c.shape[1], w.ctypes.data_as(_ip),
+                                                  sf.ctypes.data_as(_ip), c.ctypes.data_as(_dp),
+                                                  x.ctypes.data_as(_dp), lv.ctypes.data_as(_dp),
+                                                  res.ctypes.data_as(_dp)),
+                    "sw_wf_allocate_types")
+        return x, lv, float(res[0]), int(res[1]), int(res[2]), int(res[3])
+
+    def wf_allocate_types_batch(self, instances, offsets=None):
+        """sw_wf_allocate_types_batch over a list of (workers, scale_factors,
+        coefficients) tuples with one number of types, one kernel launch;
+        returns the list of (x [m, n], levels [m], last level, Newton steps,
+        stages, flags).  offsets (tests only) overrides the CSR offsets built
+        from the instances."""
+        parts = [self._wf_types_arrays(*inst) for inst in instances]
+        count = len(parts)
+        n = len(parts[0][0]) if parts else 1
+        if any(len(p[0]) != n for p in parts):
+            raise ValueError("every instance must have the same number of worker types")
+        off = np.zeros(count + 1, dtype=np.int64)
+        for i, p in enumerate(parts):
+            off[i + 1] = off[i] + len(p[1])
+
+        def cat(c, dtype):
+            return np.ascontiguousarray(np.concatenate([p[c].reshape(-1) for p in parts]) if parts else [], dtype=dtype)
+
+        w, sf, cf = cat(0, np.int32), cat(1, np.int32), cat(2, np.float64)
+        x = np.zeros(len(cf), dtype=np.float64)
+        lv = np.zeros(len(sf), dtype=np.float64)
+        res = np.zeros((count, 4), dtype=np.float64)
+        coff = off if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
+        self._check(self.lib.sw_wf_allocate_types_batch(
+            self.h, count, n, coff.ctypes.data_as(C.POINTER(C.c_int64)), w.ctypes.data_as(_ip),
+            sf.ctypes.data_as(_ip), cf.ctypes.data_as(_dp), x.ctypes.data_as(_dp), lv.ctypes.data_as(_dp),
+            res.ctypes.data_as(_dp)), "sw_wf_allocate_types_batch")
+        return [(x[off[i] * n:off[i + 1] * n].reshape(-1, n).copy(), lv[off[i]:off[i + 1]].copy(), float(res[i, 0]),
+                 int(res[i, 1]), int(res[i, 2]), int(res[i, 3])) for i in range(count)]
 
     # ---- the per-job allocation policies (csrc/sw_alloc.h; _ALLOC above) ----
     @staticmethod
