@@ -31,6 +31,7 @@
 
 #include "../../include/shockwave_amd.h"
 #include "sw_arith.h"
+#include "sw_keyarith.h"
 #include "sw_rowsearch.h"
 #include "sw_block.h"
 #include "sw_device.h"
@@ -146,6 +147,10 @@ struct Ctx {
     int32_t N, T, G, nb, q;
     int64_t C;
     double k, A;
+    /* No key is a NaN (bits above +inf's, a row out of order).  sw_key makes
+     * one only from 0·∞, where 1/(w·A) overflows: that takes a subnormal A.
+     * Set by setup (uniform). */
+    uint32_t kfin;
     double inv_delta; /* 1 / Δ: the slope of g(n) ≈ R − Δ·n (d·rate = Δ) */
     int64_t passes;
     double lsU, lsM; /* utility / makespan of the level search's best counts */
@@ -200,6 +205,7 @@ struct Ctx {
         k = I->k;
         inv_delta = 1.0 / I->delta;
         passes = 0;
+        kfin = 0;
         q = (N + SW_BLOCK - 1) / SW_BLOCK;
         w_in = B.w + I->job_off;
         p_in = B.p + I->job_off;
@@ -464,6 +470,7 @@ struct Ctx {
         double amax = 0.0;
         for_jobs([&](int j, int s) { amax = sw_max(amax, jc(j, s).a); });
         A = blk.dmax(amax);
+        kfin = sw_uni((uint32_t)(!(A > 0.0) || A >= 2.2250738585072014e-308));
         if constexpr (ONE) {
             /* rolled evaluation into an LDS staging window (SW_SETUP_CH keys
              * × SW_JPT jobs per thread per chunk), then compile-time-indexed
@@ -476,7 +483,8 @@ struct Ctx {
              * each job keeps its segment's (β_b, ℓ_b, slope_b) and the next
              * breakpoint in registers and re-reads them from LDS only when u
              * crosses a breakpoint.  Same operations on the same operands as
-             * sw_f, so the same bits. */
+             * sw_f, so the same bits; the three minima per key are the one-
+             * instruction forms of sw_keyarith.h (same bits again). */
             int sb[SW_JPT];
             double sbeta[SW_JPT], sell[SW_JPT], sslope[SW_JPT], snext[SW_JPT];
             auto seg_load = [&](int s, int b) {
@@ -487,7 +495,7 @@ struct Ctx {
                 snext[s] = b + 1 <= nb - 2 ? beta[b + 1] : __builtin_inf();
             };
             auto f_inc = [&](int s, const sw_jobc& cj, int n) {
-                const double u = (cj.Fd + sw_e(&cj, n)) * cj.invE;
+                const double u = (cj.Fd + sw_e_nf(&cj, n)) * cj.invE;
                 while (snext[s] <= u) seg_load(s, sb[s] + 1);
                 return cj.a * (sell[s] + sslope[s] * (u - sbeta[s]));
             };
@@ -512,8 +520,8 @@ struct Ctx {
                         if (act && n < T && cs.w <= G) {
                             const double cur = f_inc(s, cs, n + 1);
                             const double v = sw_pos(cur - prev[s]);
-                            vm[s] = (n == 0) ? v : sw_min(vm[s], v);
-                            kv = sw_key(vm[s], ksc[s]);
+                            vm[s] = (n == 0) ? v : sw_min_nf(vm[s], v);
+                            kv = sw_key_nf(vm[s], ksc[s]);
                             prev[s] = cur;
                         }
                         stage[(s * CH + i) * SW_BLOCK + threadIdx.x] = kv;
@@ -567,6 +575,8 @@ struct Ctx {
         const int64_t bud = C - Wf;
         double rho_d = 0.0;
         int64_t wgt_star;
+        /* the price loop's per-job windows (ONE), kept for the tie group */
+        int ca[SW_JPT], cb[SW_JPT];
         if (Wall <= bud) {
             for_jobs([&](int j, int s) {
                 ncur[j] = (uint8_t)Tj(j, s);
@@ -580,15 +590,22 @@ struct Ctx {
                  * cb = #keys > hi.  Every probe mid ∈ [lo, hi) counts
                  * between them, so a job whose window is closed (ca == cb)
                  * skips its row search; as the bracket narrows, whole
-                 * waves skip.  Same probes, same ρ*. */
-                int ca[SW_JPT], cb[SW_JPT], cm[SW_JPT];
+                 * waves skip.  Same probes, same ρ*.
+                 * The first two calls of an instance enter with lo = 0, where
+                 * every key counts (bits ≥ 0: Tj − l), and the first with
+                 * hi = +inf, above every key (0): no search for those, unless
+                 * a key can be a NaN (kfin). */
+                int cm[SW_JPT];
 #pragma unroll
                 for (int s = 0; s < SW_JPT; ++s) { ca[s] = 0; cb[s] = 0; cm[s] = 0; }
-                if (lo < hi)
-                    for_jobs([&](int j, int s) {
-                        ca[s] = cnt<true>(j, s, lo, lcur[j]);
-                        cb[s] = cnt<false>(j, s, hi, lcur[j]);
-                    });
+                if (lo < hi) {
+                    if (lo == 0)
+                        for_jobs([&](int j, int s) { ca[s] = Tj(j, s) - lcur[j]; });
+                    else
+                        for_jobs([&](int j, int s) { ca[s] = cnt<true>(j, s, lo, lcur[j]); });
+                    if (hi != SW_KEY_INF_BITS || !kfin)
+                        for_jobs([&](int j, int s) { cb[s] = cnt<false>(j, s, hi, lcur[j]); });
+                }
                 /* Snapped to key values (twin: select_level): the open
                  * jobs also report the keys either side of mid, W is
                  * constant between them, and the bracket jumps there.
@@ -654,14 +671,27 @@ struct Ctx {
             rho_d = (double)sw_float_of(rho);
             int64_t wt_l = 0;
             int32_t tie_l = 0;
-            for_jobs([&](int j, int s) {
-                const int tk = cnt<false>(j, s, rho, lcur[j]);
-                const int tie = cnt<true>(j, s, rho, lcur[j]) - tk;
+            auto tie_put = [&](int j, int s, int tk, int tie) {
                 tkcur[j] = (uint8_t)tk;
                 tiecur[j] = (uint8_t)tie;
                 wt_l += (int64_t)jc(j, s).w * tk;
                 tie_l += jc(j, s).w * tie;
-            });
+            };
+            if (ONE && plo < phi && kfin) {
+                /* The loop ended with lo == hi == ρ* and its windows exact at
+                 * both ends: cb = #keys > ρ*, ca = #keys ≥ ρ* (after a down
+                 * probe no open job has a key in (hi, mid], after an up probe
+                 * none in (mid, lo), a closed job none in [lo, hi] at all) —
+                 * the two searches' results. */
+                for_jobs([&](int j, int s) { tie_put(j, s, cb[s], ca[s] - cb[s]); });
+            } else {
+                /* the loop never ran (plo == phi on entry): no windows; or
+                 * a row can be out of order, and the searches decide */
+                for_jobs([&](int j, int s) {
+                    const int tk = cnt<false>(j, s, rho, lcur[j]);
+                    tie_put(j, s, tk, cnt<true>(j, s, rho, lcur[j]) - tk);
+                });
+            }
             const int64_t wt = blk.sum(wt_l);
             wgt_star = wt;
             const int64_t rem = bud - wt;
