@@ -211,11 +211,8 @@ void sw_destroy(sw_handle* h) {
     if (h->dn) (void)hipStreamSynchronize(h->dn);
     sw_shard_release(h);
     sw_mmf_release(h);
-    sw_mmfc_release(h);
-    sw_mtdt_release(h);
-    sw_ftft_release(h);
-    sw_wft_release(h);
     sw_io_release(h);
+    sw_types_release(h);
     h->d_in.release(); h->d_res.release();
     h->d_ws_u8.release(); h->d_ws_u64.release(); h->d_ws_sort.release();
     h->d_ws_keys.release(); h->d_ws_jc.release(); h->d_stamps.release();

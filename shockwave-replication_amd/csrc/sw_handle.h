@@ -66,6 +66,14 @@ struct sw_io_bufs {
     HostBuf<unsigned char> hin, hout;
 };
 
+/* The per-job workspace of the interior-point engine and the instances'
+ * normalising shifts: one set for the four worker-type calls (sw_types.h), under
+ * the argument of sw_io_bufs. */
+struct sw_types_bufs {
+    DevBuf<double> ws;
+    std::vector<int32_t> shifts;
+};
+
 struct sw_handle {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -136,16 +144,10 @@ struct sw_handle {
     sw_shard_state* shard = nullptr;
     /* MaxMinFairness allocation buffers (sw_mmf.hip) */
     void* mmf = nullptr;
-    /* the workspace of the centred worker-type MaxMinFairness call (sw_mmf_ipm.hip) */
-    void* mmfc = nullptr;
-    /* the workspace of the worker-type MinTotalDuration call (sw_mtd_types.hip) */
-    void* mtdt = nullptr;
-    /* the workspace of the worker-type FinishTimeFairness call (sw_ftf_types.hip) */
-    void* ftft = nullptr;
-    /* the workspace of the worker-type water-filling call (sw_wf_types.hip) */
-    void* wft = nullptr;
     /* the blocks of the per-job allocation policies (sw_alloc.h) and of AlloX (sw_allox.hip) */
     sw_io_bufs io;
+    /* the engine's workspace and the shifts of the worker-type calls (sw_types.h) */
+    sw_types_bufs types;
 };
 
 /* records a call's error text in the handle; SW_HIP does so for a failed HIP call */
@@ -165,16 +167,10 @@ inline int sw_fail(sw_handle* h, int code, const std::string& msg) {
 void sw_shard_release(sw_handle* h);
 /* sw_mmf.hip: frees the MaxMinFairness buffers */
 void sw_mmf_release(sw_handle* h);
-/* sw_mmf_ipm.hip: frees the centred call's workspace */
-void sw_mmfc_release(sw_handle* h);
-/* sw_mtd_types.hip: frees the worker-type MinTotalDuration call's workspace */
-void sw_mtdt_release(sw_handle* h);
-/* sw_ftf_types.hip: frees the worker-type FinishTimeFairness call's workspace */
-void sw_ftft_release(sw_handle* h);
-/* sw_wf_types.hip: frees the worker-type water-filling call's workspace */
-void sw_wft_release(sw_handle* h);
 /* frees the shared input / output blocks */
 inline void sw_io_release(sw_handle* h) {
     h->io.in.release(); h->io.out.release(); h->io.hin.release(); h->io.hout.release();
 }
+/* frees the worker-type calls' workspace */
+inline void sw_types_release(sw_handle* h) { h->types.ws.release(); }
 

@@ -595,6 +595,32 @@ class Solver:
             raise ValueError("coefficients must be [num_jobs][num_types]")
         return w, sf, c
 
+    def _types_batch(self, what, arrays, ncols, instances, offsets, width, levels=False):
+        """sw_<what>_batch over a list of per-instance argument tuples with one
+        number of types (arrays: the policy's check of one instance, returning
+        ncols arrays: workers, scale factors, the [m, n] column, then the [m]
+        columns); returns per instance (x [m, n], levels [m] if the policy has
+        them, the width result words)."""
+        parts = [arrays(*inst) for inst in instances]
+        count = len(parts)
+        n = len(parts[0][0]) if parts else 1
+        if any(len(p[0]) != n for p in parts):
+            raise ValueError("every instance must have the same number of worker types")
+        off = np.zeros(count + 1, dtype=np.int64)
+        for i, p in enumerate(parts):
+            off[i + 1] = off[i] + len(p[1])
+        cat = [np.ascontiguousarray(np.concatenate([p[c].reshape(-1) for p in parts]) if parts else [],
+                                    dtype=np.int32 if c < 2 else np.float64) for c in range(ncols)]
+        x = np.zeros(len(cat[2]), dtype=np.float64)
+        lv = np.zeros(len(cat[1]), dtype=np.float64)
+        res = np.zeros((count, width), dtype=np.float64)
+        coff = off if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
+        outs = [x, lv, res] if levels else [x, res]
+        self._check(getattr(self.lib, what)(self.h, count, n, coff.ctypes.data_as(C.POINTER(C.c_int64)),
+                                            *map(self._ptr, cat + outs)), what)
+        return [(x[off[i] * n:off[i + 1] * n].reshape(-1, n).copy(),) +
+                ((lv[off[i]:off[i + 1]].copy(),) if levels else ()) + (res[i],) for i in range(count)]
+
     def mmf_allocate_types_centred(self, workers, scale_factors, coefficients):
         """The LP of mmf_allocate_types with the analytic centre of its optimal
         face as the allocation, the point ECOS converges to
@@ -613,26 +639,8 @@ class Solver:
         scale_factors, coefficients) tuples with one number of types, one kernel
         launch; returns the list of (x [m, n], t*, Newton steps).  offsets
         (tests only) overrides the CSR offsets built from the instances."""
-        parts = [self._mmf_types_arrays(*inst) for inst in instances]
-        count = len(parts)
-        n = len(parts[0][0]) if parts else 1
-        if any(len(w) != n for w, _, _ in parts):
-            raise ValueError("every instance must have the same number of worker types")
-        off = np.zeros(count + 1, dtype=np.int64)
-        for i, (_, sf, _) in enumerate(parts):
-            off[i + 1] = off[i] + len(sf)
-        w = np.ascontiguousarray(np.concatenate([p[0] for p in parts]) if parts else [], dtype=np.int32)
-        sf = np.ascontiguousarray(np.concatenate([p[1] for p in parts]) if parts else [], dtype=np.int32)
-        c = np.ascontiguousarray(np.concatenate([p[2].reshape(-1) for p in parts]) if parts else [], dtype=np.float64)
-        x = np.zeros(len(c), dtype=np.float64)
-        lvl = np.zeros((count, 2), dtype=np.float64)
-        coff = off if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
-        self._check(self.lib.sw_mmf_allocate_types_centred_batch(
-            self.h, count, n, coff.ctypes.data_as(C.POINTER(C.c_int64)), w.ctypes.data_as(_ip),
-            sf.ctypes.data_as(_ip), c.ctypes.data_as(_dp), x.ctypes.data_as(_dp), lvl.ctypes.data_as(_dp)),
-            "sw_mmf_allocate_types_centred_batch")
-        return [(x[off[i] * n:off[i + 1] * n].reshape(-1, n).copy(), float(lvl[i, 0]), int(lvl[i, 1]))
-                for i in range(count)]
+        return [(x, float(r[0]), int(r[1])) for x, r in self._types_batch(
+            "sw_mmf_allocate_types_centred_batch", self._mmf_types_arrays, 3, instances, offsets, 2)]
 
     # ---- MinTotalDuration over worker types that differ (csrc/sw_mtd_types.h) ----
     MTDT_IDLE = 1  # flags of mtd_allocate_types: no job has steps left
@@ -668,28 +676,8 @@ class Solver:
         throughputs, steps) tuples with one number of types, one kernel launch;
         returns the list of (x [m, n], T, t*, Newton steps, flags).  offsets
         (tests only) overrides the CSR offsets built from the instances."""
-        parts = [self._mtd_types_arrays(*inst) for inst in instances]
-        count = len(parts)
-        n = len(parts[0][0]) if parts else 1
-        if any(len(p[0]) != n for p in parts):
-            raise ValueError("every instance must have the same number of worker types")
-        off = np.zeros(count + 1, dtype=np.int64)
-        for i, p in enumerate(parts):
-            off[i + 1] = off[i] + len(p[1])
-        w = np.ascontiguousarray(np.concatenate([p[0] for p in parts]) if parts else [], dtype=np.int32)
-        sf = np.ascontiguousarray(np.concatenate([p[1] for p in parts]) if parts else [], dtype=np.int32)
-        thr = np.ascontiguousarray(np.concatenate([p[2].reshape(-1) for p in parts]) if parts else [],
-                                   dtype=np.float64)
-        st = np.ascontiguousarray(np.concatenate([p[3] for p in parts]) if parts else [], dtype=np.float64)
-        x = np.zeros(len(thr), dtype=np.float64)
-        res = np.zeros((count, 4), dtype=np.float64)
-        coff = off if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
-        self._check(self.lib.sw_mtd_allocate_types_batch(
-            self.h, count, n, coff.ctypes.data_as(C.POINTER(C.c_int64)), w.ctypes.data_as(_ip),
-            sf.ctypes.data_as(_ip), thr.ctypes.data_as(_dp), st.ctypes.data_as(_dp), x.ctypes.data_as(_dp),
-            res.ctypes.data_as(_dp)), "sw_mtd_allocate_types_batch")
-        return [(x[off[i] * n:off[i + 1] * n].reshape(-1, n).copy(), float(res[i, 0]), float(res[i, 1]),
-                 int(res[i, 2]), int(res[i, 3])) for i in range(count)]
+        return [(x, float(r[0]), float(r[1]), int(r[2]), int(r[3])) for x, r in self._types_batch(
+            "sw_mtd_allocate_types_batch", self._mtd_types_arrays, 4, instances, offsets, 4)]
 
     # ---- FinishTimeFairness over worker types that differ (csrc/sw_ftf_types.h) ----
     FTFT_BOX = 1   # flags of ftf_allocate_types: ρ* is the least level the time rows admit
@@ -729,42 +717,12 @@ class Solver:
         one kernel launch; returns the list of (x [m, n], ρ*, t*(ρ*), Newton
         steps, level solves, flags).  offsets (tests only) overrides the CSR
         offsets built from the instances."""
-        parts = [self._ftf_types_arrays(*inst) for inst in instances]
-        count = len(parts)
-        n = len(parts[0][0]) if parts else 1
-        if any(len(p[0]) != n for p in parts):
-            raise ValueError("every instance must have the same number of worker types")
-        off = np.zeros(count + 1, dtype=np.int64)
-        for i, p in enumerate(parts):
-            off[i + 1] = off[i] + len(p[1])
-
-        def cat(c, dtype):
-            return np.ascontiguousarray(np.concatenate([p[c].reshape(-1) for p in parts]) if parts else [], dtype=dtype)
-
-        w, sf, thr = cat(0, np.int32), cat(1, np.int32), cat(2, np.float64)
-        st, el, ex = cat(3, np.float64), cat(4, np.float64), cat(5, np.float64)
-        x = np.zeros(len(thr), dtype=np.float64)
-        res = np.zeros((count, 5), dtype=np.float64)
-        coff = off if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
-        self._check(self.lib.sw_ftf_allocate_types_batch(
-            self.h, count, n, coff.ctypes.data_as(C.POINTER(C.c_int64)), w.ctypes.data_as(_ip),
-            sf.ctypes.data_as(_ip), thr.ctypes.data_as(_dp), st.ctypes.data_as(_dp), el.ctypes.data_as(_dp),
-            ex.ctypes.data_as(_dp), x.ctypes.data_as(_dp), res.ctypes.data_as(_dp)), "sw_ftf_allocate_types_batch")
-        return [(x[off[i] * n:off[i + 1] * n].reshape(-1, n).copy(), float(res[i, 0]), float(res[i, 1]),
-                 int(res[i, 2]), int(res[i, 3]), int(res[i, 4])) for i in range(count)]
+        return [(x, float(r[0]), float(r[1]), int(r[2]), int(r[3]), int(r[4])) for x, r in self._types_batch(
+            "sw_ftf_allocate_types_batch", self._ftf_types_arrays, 6, instances, offsets, 5)]
 
     WFT_ONE = 1   # flags of wf_allocate_types: a single stage froze every job
     WFT_NEAR = 2  # a job's statistic came within a factor 10 of the bottleneck threshold
     WFT_COARSE = 4  # a stage's solve broke down and was done again at a larger ease and path point
-
-    @staticmethod
-    def _wf_types_arrays(workers, scale_factors, coefficients):
-        w = np.ascontiguousarray(workers, dtype=np.int32)
-        sf = np.ascontiguousarray(scale_factors, dtype=np.int32)
-        c = np.ascontiguousarray(coefficients, dtype=np.float64)
-        if c.ndim != 2 or c.shape != (len(sf), len(w)):
-            raise ValueError("coefficients must be [num_jobs][num_types]")
-        return w, sf, c
 
     def wf_allocate_types(self, workers, scale_factors, coefficients):
         """The water-filling MaxMinFairness allocation over worker types whose
@@ -772,7 +730,7 @@ class Solver:
         vector of Σ_k coefficients·x by stages and the analytic centre of the
         last stage's optimal face; returns (x [m, n], levels [m], last level,
         Newton steps, stages, flags)."""
-        w, sf, c = self._wf_types_arrays(workers, scale_factors, coefficients)
+        w, sf, c = self._mmf_types_arrays(workers, scale_factors, coefficients)
         x = np.zeros(c.shape, dtype=np.float64)
         lv = np.zeros(c.shape[0], dtype=np.float64)
         res = np.zeros(4, dtype=np.float64)
@@ -789,29 +747,8 @@ class Solver:
         returns the list of (x [m, n], levels [m], last level, Newton steps,
         stages, flags).  offsets (tests only) overrides the CSR offsets built
         from the instances."""
-        parts = [self._wf_types_arrays(*inst) for inst in instances]
-        count = len(parts)
-        n = len(parts[0][0]) if parts else 1
-        if any(len(p[0]) != n for p in parts):
-            raise ValueError("every instance must have the same number of worker types")
-        off = np.zeros(count + 1, dtype=np.int64)
-        for i, p in enumerate(parts):
-            off[i + 1] = off[i] + len(p[1])
-
-        def cat(c, dtype):
-            return np.ascontiguousarray(np.concatenate([p[c].reshape(-1) for p in parts]) if parts else [], dtype=dtype)
-
-        w, sf, cf = cat(0, np.int32), cat(1, np.int32), cat(2, np.float64)
-        x = np.zeros(len(cf), dtype=np.float64)
-        lv = np.zeros(len(sf), dtype=np.float64)
-        res = np.zeros((count, 4), dtype=np.float64)
-        coff = off if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
-        self._check(self.lib.sw_wf_allocate_types_batch(
-            self.h, count, n, coff.ctypes.data_as(C.POINTER(C.c_int64)), w.ctypes.data_as(_ip),
-            sf.ctypes.data_as(_ip), cf.ctypes.data_as(_dp), x.ctypes.data_as(_dp), lv.ctypes.data_as(_dp),
-            res.ctypes.data_as(_dp)), "sw_wf_allocate_types_batch")
-        return [(x[off[i] * n:off[i + 1] * n].reshape(-1, n).copy(), lv[off[i]:off[i + 1]].copy(), float(res[i, 0]),
-                 int(res[i, 1]), int(res[i, 2]), int(res[i, 3])) for i in range(count)]
+        return [(x, lv, float(r[0]), int(r[1]), int(r[2]), int(r[3])) for x, lv, r in self._types_batch(
+            "sw_wf_allocate_types_batch", self._mmf_types_arrays, 3, instances, offsets, 4, levels=True)]
 
     # ---- the per-job allocation policies (csrc/sw_alloc.h; _ALLOC above) ----
     @staticmethod

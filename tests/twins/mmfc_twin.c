@@ -15,25 +15,7 @@
 
 #include "../../shockwave-replication_amd/csrc/sw_arith.h"
 #include "../../shockwave-replication_amd/csrc/sw_mmf_ipm.h"
-#include "twin_detsum.h"
-
-#define NEG_HUGE (-1.7976931348623157e308)
-
-typedef struct {
-    int32_t m;
-    double* val; /* [SW_IPM_NRED][m] */
-    double mx[SW_IPM_NMAX];
-} red;
-
-static void red_begin(red* r) {
-    for (int i = 0; i < SW_IPM_NMAX; ++i) r->mx[i] = NEG_HUGE;
-}
-static void red_max(red* r, const double* v, int cnt) {
-    for (int i = 0; i < cnt; ++i) r->mx[i] = v[i] > r->mx[i] ? v[i] : r->mx[i];
-}
-static void red_sums(const red* r, int cnt, double* out) {
-    for (int i = 0; i < cnt; ++i) out[i] = detsum(r->val + (size_t)i * r->m, r->m);
-}
+#include "twin_ipm.h"
 
 /* the shift of the normalisation: from the largest coefficient on a type with
  * workers (the host does this for the kernel while it validates) */
@@ -67,8 +49,6 @@ int mmfc_twin_allocate(int32_t m, int32_t n, const int32_t* workers, const int32
     R.val = (double*)malloc(sizeof(double) * (size_t)SW_IPM_NRED * m);
     if (!ws || !R.val) { free(ws); free(R.val); return -1; }
     sw_ipm_job J = {ws, m, 0, na, 0.0};
-#define EACH_JOB for (J.j = 0; J.j < m; ++J.j) if ((J.sf = (double)sf[J.j]), 1)
-#define PUT(cnt) for (int i_ = 0; i_ < (cnt); ++i_) R.val[(size_t)i_ * m + J.j] = sums[i_]
 
     red_begin(&R);
     EACH_JOB {
@@ -79,44 +59,9 @@ int mmfc_twin_allocate(int32_t m, int32_t n, const int32_t* workers, const int32
     red_sums(&R, 2, sums);
     sw_ipm_glob_load(g, sums, R.mx);
 
-    red_begin(&R);
-    EACH_JOB {
-        sw_ipm_job_start(g, &J, mx);
-        red_max(&R, mx, 1);
-    }
-    sw_ipm_glob_start(g, R.mx);
-    EACH_JOB sw_ipm_job_start2(g, &J);
+    twin_ipm_start_tail(g, R, J, sf, m);
 
-    for (;;) {
-        red_begin(&R);
-        EACH_JOB {
-            sw_ipm_job_resid(g, &J, sums, mx);
-            PUT(na + 2);
-            red_max(&R, mx, 3);
-        }
-        red_sums(&R, na + 2, sums);
-        sw_ipm_glob_resid(g, sums, R.mx);
-        if (g->done) break;
-        EACH_JOB sw_ipm_job_prep(g, &J);
-        for (int32_t k = 0; k < na; ++k) {
-            const int32_t cnt = sw_ipm_row_count(na, k, g->has_t);
-            EACH_JOB {
-                const sw_ipm_rowctx rc = sw_ipm_row_begin(&J, k);
-                for (int32_t i = 0; i < cnt; ++i) R.val[(size_t)i * m + J.j] = sw_ipm_row_val(&J, &rc, i);
-            }
-            red_sums(&R, cnt, sums);
-            sw_ipm_glob_row(g, k, sums);
-        }
-        sw_ipm_glob_solve(g);
-        if (g->done) break;
-        red_begin(&R);
-        EACH_JOB {
-            sw_ipm_job_back(g, &J, mx);
-            red_max(&R, mx, 2);
-        }
-        sw_ipm_glob_step(g, R.mx);
-        EACH_JOB sw_ipm_job_step(g, &J);
-    }
+    twin_ipm_solve(g, R, J, sf, m);
     if (sw_ipm_two_points(g)) {
         red_begin(&R);
         EACH_JOB {
