@@ -38,10 +38,10 @@ import math
 
 import numpy as np
 
-import sw_native
+from sw_policy import Policy
 
 
-class AlloXPolicy:
+class AlloXPolicy(Policy):
     """allox.py:13-141."""
 
     def __init__(self, alpha=1.0, native=None):
@@ -50,15 +50,6 @@ class AlloXPolicy:
         self._prev_allocation = {}
         self._native = native
         self.last_cost = None  # total cost of the last assignment
-
-    @property
-    def name(self):
-        return self._name
-
-    def _engine(self):
-        if self._native is None:
-            self._native = sw_native.Solver(device=0)
-        return self._native
 
     def get_allocation(self, unflattened_throughputs, scale_factors, times_since_start,
                        num_steps_remaining, cluster_spec):

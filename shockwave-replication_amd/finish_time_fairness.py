@@ -40,20 +40,8 @@ import copy
 
 import numpy as np
 
-import sw_native
-
-
-def _flatten(d, cluster_spec):
-    """policy.py:28-44: jobs sorted by id, worker types sorted by name (from
-    the first job), the throughput matrix."""
-    job_ids = sorted(d.keys())
-    if len(job_ids) == 0:
-        return None, None
-    worker_types = sorted(d[job_ids[0]].keys())
-    if len(worker_types) == 0:
-        return None, None
-    m = np.array([[d[j][wt] for wt in worker_types] for j in job_ids], dtype=np.float64)
-    return m, (job_ids, worker_types)
+from sw_policy import Policy, clipped, identical_types, int_workers, split_over_types, with_v100_throughputs
+from sw_policy import flatten as _flatten, unflatten as _unflatten
 
 
 def _isolated_throughputs(throughputs, index, scale_factors, cluster_spec):
@@ -70,7 +58,7 @@ def _isolated_throughputs(throughputs, index, scale_factors, cluster_spec):
     return np.sum(np.multiply(throughputs, x), axis=1)
 
 
-class FinishTimeFairnessPolicyWithPerf:
+class FinishTimeFairnessPolicyWithPerf(Policy):
     """finish_time_fairness.py:55-140."""
 
     def __init__(self, solver="ECOS", native=None, worker_types=False):
@@ -83,26 +71,17 @@ class FinishTimeFairnessPolicyWithPerf:
         self._num_steps_remaining_prev_iteration = {}
         self.last_level = None  # (ρ*, μ) of the last solve; (ρ*, level solves) of one over differing types
 
-    @property
-    def name(self):
-        return self._name
-
-    def _engine(self):
-        if self._native is None:
-            self._native = sw_native.Solver(device=0)
-        return self._native
-
     def get_allocation(self, unflattened_throughputs, scale_factors, unflattened_priority_weights,
                        times_since_start, num_steps_remaining, cluster_spec):
-        throughputs, index = _flatten(unflattened_throughputs, cluster_spec)
+        throughputs, index = _flatten(unflattened_throughputs)
         if throughputs is None:
             self._isolated_throughputs_prev_iteration = {}
             self._num_steps_remaining_prev_iteration = {}
             return None
         m, n = throughputs.shape
         job_ids, worker_types = index
-        workers = [int(cluster_spec[wt]) for wt in worker_types]
-        over_types = not (throughputs == throughputs[:, :1]).all()
+        workers = int_workers(worker_types, cluster_spec)
+        over_types = not identical_types(throughputs)
         if over_types and not self._worker_types:
             raise NotImplementedError(
                 "FinishTimeFairness with throughputs that differ by worker type is not supported: "
@@ -143,20 +122,15 @@ class FinishTimeFairnessPolicyWithPerf:
             x, rho, _, _, solves, _ = self._engine().ftf_allocate_types(
                 np.array(workers, dtype=np.int32), sf, throughputs, steps, elapsed, expected)
             self.last_level = (rho, solves)
-            xs = np.asarray(x, dtype=np.float64).reshape(m, n).clip(min=0.0).clip(max=1.0)
-            return {job_ids[i]: {worker_types[k]: xs[i, k] for k in range(n)} for i in range(m)}
+            return _unflatten(clipped(np.asarray(x, dtype=np.float64).reshape(m, n)), index)
         x, rho, mu = self._engine().ftf_allocate(sf, full_time, elapsed, expected, total)
         self.last_level = (rho, mu)
         x = np.asarray(x, dtype=np.float64)
-        if n == 1:
-            xs = x.reshape(m, 1)
-        else:
-            xs = np.array([[x[i] * workers[k] / total for k in range(n)] for i in range(m)])
-        xs = xs.clip(min=0.0).clip(max=1.0)
-        return {job_ids[i]: {worker_types[k]: xs[i, k] for k in range(n)} for i in range(m)}
+        xs = split_over_types(x, workers, total)
+        return _unflatten(clipped(xs), index)
 
 
-class FinishTimeFairnessPolicy:
+class FinishTimeFairnessPolicy(Policy):
     """finish_time_fairness.py:14-52: the WithPerf policy with every worker
     type's throughput replaced by the job's v100 throughput."""
 
@@ -164,20 +138,11 @@ class FinishTimeFairnessPolicy:
         self._name = "FinishTimeFairness"
         self._finish_time_fairness_perf_policy = FinishTimeFairnessPolicyWithPerf(solver, native)
 
-    @property
-    def name(self):
-        return self._name
-
     def get_allocation(self, unflattened_throughputs, scale_factors, unflattened_priority_weights,
                        times_since_start, num_steps_remaining, cluster_spec):
-        throughputs, _ = _flatten(unflattened_throughputs, cluster_spec)
+        throughputs, _ = _flatten(unflattened_throughputs)
         if throughputs is None:
             return None
-        new_unflattened_throughputs = {}
-        for job_id in unflattened_throughputs:
-            new_unflattened_throughputs[job_id] = {}
-            for worker_type in unflattened_throughputs[job_id]:
-                new_unflattened_throughputs[job_id][worker_type] = unflattened_throughputs[job_id]["v100"]
         return self._finish_time_fairness_perf_policy.get_allocation(
-            new_unflattened_throughputs, scale_factors, unflattened_priority_weights, times_since_start,
-            num_steps_remaining, cluster_spec)
+            with_v100_throughputs(unflattened_throughputs), scale_factors, unflattened_priority_weights,
+            times_since_start, num_steps_remaining, cluster_spec)

@@ -34,7 +34,9 @@ import warnings
 
 import numpy as np
 
-import sw_native
+from sw_policy import Policy, clipped, num_workers
+from sw_policy import flatten as _flatten, unflatten as _unflatten
+from sw_policy import proportional_throughputs as _proportional_throughputs
 
 
 class SimplexVertexWarning(UserWarning):
@@ -44,36 +46,7 @@ class SimplexVertexWarning(UserWarning):
 _WARNED = False
 
 
-def _flatten(d, cluster_spec):
-    """policy.py:28-44: jobs sorted by id, worker types sorted by name (from
-    the first job), the throughput matrix and the per-type worker counts."""
-    job_ids = sorted(d.keys())
-    if len(job_ids) == 0:
-        return None, None, None
-    worker_types = sorted(d[job_ids[0]].keys())
-    if len(worker_types) == 0:
-        return None, None, None
-    num_workers = [cluster_spec[wt] for wt in worker_types]
-    m = np.array([[d[j][wt] for wt in worker_types] for j in job_ids], dtype=np.float64)
-    return m, (job_ids, worker_types), num_workers
-
-
-def _unflatten(x, index):
-    job_ids, worker_types = index
-    return {job_ids[i]: {worker_types[k]: x[i, k] for k in range(len(worker_types))}
-            for i in range(len(job_ids))}
-
-
-def _proportional_throughputs(throughputs, worker_types, cluster_spec):
-    """ProportionalPolicy.get_throughputs (proportional.py:15-44): the cluster
-    split evenly over the jobs, each row scaled to sum to at most 1."""
-    m, _ = throughputs.shape
-    x = np.array([[cluster_spec[wt] / m for wt in worker_types] for _ in range(m)])
-    x = x / np.sum(x, axis=1).max()
-    return np.sum(np.multiply(throughputs, x), axis=1).reshape((m, 1))
-
-
-class MaxMinFairnessPolicyWithPerf:
+class MaxMinFairnessPolicyWithPerf(Policy):
     """max_min_fairness.py:37-100 (heterogeneity-aware: real throughputs)."""
 
     def __init__(self, solver="ECOS", native=None, centred=False):
@@ -82,41 +55,36 @@ class MaxMinFairnessPolicyWithPerf:
         self._native = native
         self._centred = centred  # several types: the face's analytic centre, not a vertex
 
-    def _engine(self):
-        if self._native is None:
-            self._native = sw_native.Solver(device=0)
-        return self._native
-
     def coefficients(self, unflattened_throughputs, scale_factors, unflattened_priority_weights,
                      cluster_spec):
         """The LP's coefficient matrix, in the reference's float operations
         (max_min_fairness.py:54-87): (throughputs · priority_weights) · scale
         factors, priority_weights = 1/w_j · 1/proportional throughput."""
-        throughputs, index, num_workers = _flatten(unflattened_throughputs, cluster_spec)
+        throughputs, index = _flatten(unflattened_throughputs)
         if throughputs is None:
             return None, None, None, None
         m, n = throughputs.shape
         job_ids, worker_types = index
         sf_array = np.array([[scale_factors[job_ids[i]]] * n for i in range(m)], dtype=np.float64)
         pw = np.array([1.0 / unflattened_priority_weights[j] for j in job_ids])
-        prop = _proportional_throughputs(throughputs, worker_types, cluster_spec)
+        prop = _proportional_throughputs(throughputs, worker_types, cluster_spec).reshape((m, 1))
         pw = np.multiply(pw.reshape((m, 1)), 1.0 / prop.reshape((m, 1)))
         coef = np.multiply(throughputs * pw.reshape((m, 1)), sf_array)
         sf = np.array([scale_factors[j] for j in job_ids], dtype=np.int32)
-        return coef, sf, index, num_workers
+        return coef, sf, index, num_workers(worker_types, cluster_spec)
 
     def get_allocation(self, unflattened_throughputs, scale_factors, unflattened_priority_weights,
                        cluster_spec):
-        coef, sf, index, num_workers = self.coefficients(
+        coef, sf, index, workers = self.coefficients(
             unflattened_throughputs, scale_factors, unflattened_priority_weights, cluster_spec)
         if coef is None:
             return None
         eng = self._engine()
         if coef.shape[1] == 1 and (coef > 0.0).all():
-            x, _, _ = eng.mmf_allocate(sf, coef[:, 0], int(num_workers[0]))
+            x, _, _ = eng.mmf_allocate(sf, coef[:, 0], int(workers[0]))
             x = x.reshape(-1, 1)
         elif self._centred:
-            x, _, _ = eng.mmf_allocate_types_centred(num_workers, sf, coef)
+            x, _, _ = eng.mmf_allocate_types_centred(workers, sf, coef)
         else:
             global _WARNED
             if not _WARNED:
@@ -125,11 +93,11 @@ class MaxMinFairnessPolicyWithPerf:
                               "LP (GPU simplex); the reference's ECOS returns an interior point of the same "
                               "optimal face, so shares may differ where the optimum is not unique",
                               SimplexVertexWarning, stacklevel=2)
-            x, _, _ = eng.mmf_allocate_types(num_workers, sf, coef)
-        return _unflatten(x.clip(min=0.0).clip(max=1.0), index)
+            x, _, _ = eng.mmf_allocate_types(workers, sf, coef)
+        return _unflatten(clipped(x), index)
 
 
-class MaxMinFairnessPolicy:
+class MaxMinFairnessPolicy(Policy):
     """max_min_fairness.py:12-34: the WithPerf policy with every throughput 1.0
     (the Fig-9 "gavel" baseline)."""
 

@@ -51,33 +51,15 @@ import warnings
 import numpy as np
 
 import sw_native
+from sw_policy import Policy, clipped, identical_types, int_workers, split_over_types
+from sw_policy import flatten as _flatten, unflatten as _unflatten
+from sw_policy import proportional_throughputs as _proportional_throughputs
 
 
 class WaterFillingStageWarning(UserWarning):
     """sw_wf_allocate_types flagged its own result: a bottleneck statistic near
     its threshold (a job may have frozen a stage late or early) or a stage solved
     again at a coarser path point (levels eased by more than a part in 2^30)."""
-
-
-def _flatten(d, cluster_spec):
-    """policy.py:28-44: jobs sorted by id, worker types sorted by name (from
-    the first job), the throughput matrix."""
-    job_ids = sorted(d.keys())
-    if len(job_ids) == 0:
-        return None, None
-    worker_types = sorted(d[job_ids[0]].keys())
-    if len(worker_types) == 0:
-        return None, None
-    m = np.array([[d[j][wt] for wt in worker_types] for j in job_ids], dtype=np.float64)
-    return m, (job_ids, worker_types)
-
-
-def _proportional_throughputs(throughputs, worker_types, cluster_spec):
-    """ProportionalPolicy.get_throughputs (proportional.py:15-44)."""
-    m, _ = throughputs.shape
-    x = np.array([[cluster_spec[wt] / m for wt in worker_types] for _ in range(m)])
-    x = x / np.sum(x, axis=1).max()
-    return np.sum(np.multiply(throughputs, x), axis=1)
 
 
 def _check_reweighting(priority_reweighting_policies):
@@ -88,7 +70,7 @@ def _check_reweighting(priority_reweighting_policies):
             "max_min_fairness_water_filling_hierarchical, not by this class")
 
 
-class MaxMinFairnessWaterFillingPolicyWithPerf:
+class MaxMinFairnessWaterFillingPolicyWithPerf(Policy):
     """max_min_fairness_water_filling.py:471-556."""
 
     def __init__(self, priority_reweighting_policies=None, native=None, worker_types=False):
@@ -100,37 +82,26 @@ class MaxMinFairnessWaterFillingPolicyWithPerf:
         self.last_level = None  # (L*, Σ sf_j·x_j) of the last solve; (last level, stages) over differing types
         self.last_flags = 0  # the flags of the last sw_wf_allocate_types call (SW_WFT_NEAR, SW_WFT_COARSE)
 
-    @property
-    def name(self):
-        return self._name
-
-    def _engine(self):
-        if self._native is None:
-            self._native = sw_native.Solver(device=0)
-        return self._native
-
     def get_allocation(self, unflattened_throughputs, scale_factors, unflattened_priority_weights,
                        cluster_spec, entity_weights=None, entity_to_job_mapping=None, verbose=False,
                        return_effective_throughputs=False):
-        throughputs, index = _flatten(unflattened_throughputs, cluster_spec)
+        throughputs, index = _flatten(unflattened_throughputs)
         if throughputs is None:
             return None
-        m, n = throughputs.shape
         job_ids, worker_types = index
-        if not (throughputs == throughputs[:, :1]).all():
+        if not identical_types(throughputs):
             if not self._worker_types:
                 raise NotImplementedError(
                     "water filling with throughputs that differ by worker type is not supported: "
                     "the native kernel solves one worker type (or several identical ones)")
-            return self._allocate_types(throughputs, job_ids, worker_types, scale_factors,
-                                        unflattened_priority_weights, cluster_spec, verbose,
-                                        return_effective_throughputs)
+            return self._allocate_types(throughputs, index, scale_factors, unflattened_priority_weights,
+                                        cluster_spec, verbose, return_effective_throughputs)
         for i, j in enumerate(job_ids):
             if throughputs[i, 0] == 0:
                 raise ValueError(f"job {j} has zero throughput: its normalised throughput is undefined")
             if not unflattened_priority_weights[j] > 0:
                 raise ValueError(f"job {j} has priority weight {unflattened_priority_weights[j]!r} <= 0")
-        workers = [int(cluster_spec[wt]) for wt in worker_types]
+        workers = int_workers(worker_types, cluster_spec)
         total = sum(workers)
         sf = np.array([scale_factors[j] for j in job_ids], dtype=np.int32)
         # mult_j = (1 / w_j) · sf_j in the reference's float operations (:336-345, :146-148)
@@ -142,21 +113,16 @@ class MaxMinFairnessWaterFillingPolicyWithPerf:
         if verbose:
             print("Normalized effective throughputs:", x)
             print("Water level:", level, "allocated workers:", used)
-        if n == 1:
-            xs = x.reshape(m, 1)
-        else:
-            xs = np.array([[x[i] * workers[k] / total for k in range(n)] for i in range(m)])
+        xs = split_over_types(x, workers, total)
         if return_effective_throughputs:
             return np.sum(xs, axis=1), job_ids
-        xs = xs.clip(min=0.0).clip(max=1.0)
-        return {job_ids[i]: {worker_types[k]: xs[i, k] for k in range(n)} for i in range(m)}
+        return _unflatten(clipped(xs), index)
 
-
-    def _allocate_types(self, throughputs, job_ids, worker_types, scale_factors, priority_weights, cluster_spec,
-                        verbose, return_effective_throughputs):
+    def _allocate_types(self, throughputs, index, scale_factors, priority_weights, cluster_spec, verbose,
+                        return_effective_throughputs):
         """:303-409 over throughputs that differ by worker type."""
-        m, n = throughputs.shape
-        workers = np.array([int(cluster_spec[wt]) for wt in worker_types], dtype=np.int32)
+        job_ids, worker_types = index
+        workers = np.array(int_workers(worker_types, cluster_spec), dtype=np.int32)
         for i, j in enumerate(job_ids):
             if not (throughputs[i, workers > 0] > 0).any():
                 raise ValueError(f"job {j} has no throughput on a worker type that has workers: "
@@ -183,11 +149,10 @@ class MaxMinFairnessWaterFillingPolicyWithPerf:
             print("Last water level:", level, "stages:", stages)
         if return_effective_throughputs:
             return np.sum(np.multiply(throughputs, x), axis=1) / prop, job_ids
-        x = x.clip(min=0.0).clip(max=1.0)
-        return {job_ids[i]: {worker_types[k]: x[i, k] for k in range(n)} for i in range(m)}
+        return _unflatten(clipped(x), index)
 
 
-class MaxMinFairnessWaterFillingPolicy:
+class MaxMinFairnessWaterFillingPolicy(Policy):
     """max_min_fairness_water_filling.py:412-468: the WithPerf policy with every
     throughput replaced by 1.0."""
 
@@ -198,17 +163,13 @@ class MaxMinFairnessWaterFillingPolicy:
             priority_reweighting_policies, native)
 
     @property
-    def name(self):
-        return self._name
-
-    @property
     def last_level(self):
         return self._max_min_fairness_perf_policy.last_level
 
     def get_allocation(self, unflattened_throughputs, scale_factors, unflattened_priority_weights,
                        cluster_spec, entity_weights=None, entity_to_job_mapping=None, verbose=False,
                        return_effective_throughputs=False):
-        throughputs, index = _flatten(unflattened_throughputs, cluster_spec)
+        throughputs, index = _flatten(unflattened_throughputs)
         if throughputs is None:
             return None
         job_ids, worker_types = index
@@ -221,7 +182,7 @@ class MaxMinFairnessWaterFillingPolicy:
             # :457-467: the real throughputs over the allocation, normalised by the
             # proportional ones; Σ_k x[j][k] when a job's throughputs are identical
             x = np.array([[unflattened_x[j][wt] for wt in worker_types] for j in job_ids])
-            if (throughputs == throughputs[:, :1]).all():
+            if identical_types(throughputs):
                 return np.sum(x, axis=1), job_ids
             prop = _proportional_throughputs(throughputs, worker_types, cluster_spec)
             for i, j in enumerate(job_ids):

@@ -36,13 +36,14 @@ import math
 
 import numpy as np
 
-import sw_native
-from max_min_fairness_water_filling import _flatten, _proportional_throughputs
+from sw_policy import Policy, clipped, identical_types, int_workers, split_over_types
+from sw_policy import flatten as _flatten, unflatten as _unflatten
+from sw_policy import proportional_throughputs as _proportional_throughputs
 
 _MODES = {"fairness": 0, "fifo": 1}
 
 
-class MaxMinFairnessWaterFillingHierarchicalPolicyWithPerf:
+class MaxMinFairnessWaterFillingHierarchicalPolicyWithPerf(Policy):
     """max_min_fairness_water_filling.py:471-556 with a reweighting policy per entity."""
 
     def __init__(self, priority_reweighting_policies, native=None):
@@ -56,15 +57,6 @@ class MaxMinFairnessWaterFillingHierarchicalPolicyWithPerf:
         self._native = native
         self.last_level = None  # (C*, Σ sf_j·x_j) of the last solve
         self.last_entity_capacity = None  # {entity: g_e} of the last solve
-
-    @property
-    def name(self):
-        return self._name
-
-    def _engine(self):
-        if self._native is None:
-            self._native = sw_native.Solver(device=0)
-        return self._native
 
     def _entities(self, job_ids, entity_weights, entity_to_job_mapping):
         """The entity index of every job, and the entities' ids, weights and modes."""
@@ -100,13 +92,12 @@ class MaxMinFairnessWaterFillingHierarchicalPolicyWithPerf:
     def get_allocation(self, unflattened_throughputs, scale_factors, unflattened_priority_weights,
                        cluster_spec, entity_weights=None, entity_to_job_mapping=None, verbose=False,
                        return_effective_throughputs=False):
-        throughputs, index = _flatten(unflattened_throughputs, cluster_spec)
+        throughputs, index = _flatten(unflattened_throughputs)
         if throughputs is None:
             return None
-        m, n = throughputs.shape
         job_ids, worker_types = index
         ent, entities, weights, modes = self._entities(job_ids, entity_weights, entity_to_job_mapping)
-        if not (throughputs == throughputs[:, :1]).all():
+        if not identical_types(throughputs):
             raise NotImplementedError(
                 "water filling with throughputs that differ by worker type is not supported: "
                 "the native kernel solves one worker type (or several identical ones)")
@@ -115,7 +106,7 @@ class MaxMinFairnessWaterFillingHierarchicalPolicyWithPerf:
                 raise ValueError(f"job {j} has zero throughput: its normalised throughput is undefined")
             if not unflattened_priority_weights[j] > 0:
                 raise ValueError(f"job {j} has priority weight {unflattened_priority_weights[j]!r} <= 0")
-        workers = [int(cluster_spec[wt]) for wt in worker_types]
+        workers = int_workers(worker_types, cluster_spec)
         total = sum(workers)
         sf = np.array([scale_factors[j] for j in job_ids], dtype=np.int32)
         coef = np.array([(1.0 / unflattened_priority_weights[j]) * scale_factors[j] for j in job_ids],
@@ -127,17 +118,13 @@ class MaxMinFairnessWaterFillingHierarchicalPolicyWithPerf:
         if verbose:
             print("Normalized effective throughputs:", x)
             print("Entity level:", level, "allocated workers:", used)
-        if n == 1:
-            xs = x.reshape(m, 1)
-        else:
-            xs = np.array([[x[i] * workers[k] / total for k in range(n)] for i in range(m)])
+        xs = split_over_types(x, workers, total)
         if return_effective_throughputs:
             return np.sum(xs, axis=1), job_ids
-        xs = xs.clip(min=0.0).clip(max=1.0)
-        return {job_ids[i]: {worker_types[k]: xs[i, k] for k in range(n)} for i in range(m)}
+        return _unflatten(clipped(xs), index)
 
 
-class MaxMinFairnessWaterFillingHierarchicalPolicy:
+class MaxMinFairnessWaterFillingHierarchicalPolicy(Policy):
     """max_min_fairness_water_filling.py:412-468 with a reweighting policy per
     entity: the WithPerf policy with every throughput replaced by 1.0."""
 
@@ -145,10 +132,6 @@ class MaxMinFairnessWaterFillingHierarchicalPolicy:
         self._name = "MaxMinFairnessWaterFilling"
         self._max_min_fairness_perf_policy = MaxMinFairnessWaterFillingHierarchicalPolicyWithPerf(
             priority_reweighting_policies, native)
-
-    @property
-    def name(self):
-        return self._name
 
     @property
     def last_level(self):
@@ -161,7 +144,7 @@ class MaxMinFairnessWaterFillingHierarchicalPolicy:
     def get_allocation(self, unflattened_throughputs, scale_factors, unflattened_priority_weights,
                        cluster_spec, entity_weights=None, entity_to_job_mapping=None, verbose=False,
                        return_effective_throughputs=False):
-        throughputs, index = _flatten(unflattened_throughputs, cluster_spec)
+        throughputs, index = _flatten(unflattened_throughputs)
         if throughputs is None:
             return None
         job_ids, worker_types = index
@@ -173,7 +156,7 @@ class MaxMinFairnessWaterFillingHierarchicalPolicy:
         if return_effective_throughputs:
             # :457-467: the real throughputs over the allocation, normalised by the proportional ones
             x = np.array([[unflattened_x[j][wt] for wt in worker_types] for j in job_ids])
-            if (throughputs == throughputs[:, :1]).all():
+            if identical_types(throughputs):
                 return np.sum(x, axis=1), job_ids
             prop = _proportional_throughputs(throughputs, worker_types, cluster_spec)
             for i, j in enumerate(job_ids):

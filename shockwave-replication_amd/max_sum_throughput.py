@@ -28,23 +28,11 @@ and the allocation is the one without them.  The result is clipped to [0, 1]
 """
 import numpy as np
 
-import sw_native
+from sw_policy import Policy, clipped, identical_types, int_workers, split_over_types
+from sw_policy import flatten as _flatten, unflatten as _unflatten
 
 
-def _flatten(d, cluster_spec):
-    """policy.py:28-44: jobs sorted by id, worker types sorted by name (from
-    the first job), the throughput matrix."""
-    job_ids = sorted(d.keys())
-    if len(job_ids) == 0:
-        return None, None
-    worker_types = sorted(d[job_ids[0]].keys())
-    if len(worker_types) == 0:
-        return None, None
-    m = np.array([[d[j][wt] for wt in worker_types] for j in job_ids], dtype=np.float64)
-    return m, (job_ids, worker_types)
-
-
-class ThroughputNormalizedByCostSumWithPerfSLOs:
+class ThroughputNormalizedByCostSumWithPerfSLOs(Policy):
     """max_sum_throughput.py:39-96."""
 
     def __init__(self, solver=None, native=None):
@@ -53,24 +41,15 @@ class ThroughputNormalizedByCostSumWithPerfSLOs:
         self._native = native
         self.last_level = None  # (λ, m, objective, slo_dropped) of the last solve
 
-    @property
-    def name(self):
-        return self._name
-
-    def _engine(self):
-        if self._native is None:
-            self._native = sw_native.Solver(device=0)
-        return self._native
-
     def get_allocation(self, unflattened_throughputs, scale_factors, cluster_spec, instance_costs=None,
                        SLOs={}, num_steps_remaining={}):
-        throughputs, index = _flatten(unflattened_throughputs, cluster_spec)
+        throughputs, index = _flatten(unflattened_throughputs)
         if throughputs is None:
             return None
-        m, n = throughputs.shape
+        m = len(throughputs)
         job_ids, worker_types = index
         costs = [1.0 if instance_costs is None else float(instance_costs[wt]) for wt in worker_types]
-        if not (throughputs == throughputs[:, :1]).all() or any(c != costs[0] for c in costs):
+        if not identical_types(throughputs) or any(c != costs[0] for c in costs):
             raise NotImplementedError(
                 "max sum throughput with throughputs or instance costs that differ by worker type is "
                 "not supported: the native kernel solves one worker type (or several identical ones)")
@@ -85,7 +64,7 @@ class ThroughputNormalizedByCostSumWithPerfSLOs:
                 floors = np.zeros(m, dtype=np.float64)
             if r > 0:
                 floors[i] = r / tp[i] if tp[i] > 0 else np.inf
-        workers = [int(cluster_spec[wt]) for wt in worker_types]
+        workers = int_workers(worker_types, cluster_spec)
         total = sum(workers)
         sf = np.array([scale_factors[j] for j in job_ids], dtype=np.int32)
         x, lam, mult, objective, slo_dropped = self._engine().mst_allocate(sf, weights, floors, total)
@@ -93,24 +72,16 @@ class ThroughputNormalizedByCostSumWithPerfSLOs:
         if slo_dropped:
             print("WARNING: No allocation possible with provided SLOs!")
         x = np.asarray(x, dtype=np.float64)
-        if n == 1:
-            xs = x.reshape(m, 1)
-        else:
-            xs = np.array([[x[i] * workers[k] / total for k in range(n)] for i in range(m)])
-        xs = xs.clip(min=0.0).clip(max=1.0)
-        return {job_ids[i]: {worker_types[k]: xs[i, k] for k in range(n)} for i in range(m)}
+        xs = split_over_types(x, workers, total)
+        return _unflatten(clipped(xs), index)
 
 
-class ThroughputNormalizedByCostSumWithPerf:
+class ThroughputNormalizedByCostSumWithPerf(Policy):
     """max_sum_throughput.py:23-36."""
 
     def __init__(self, solver=None, native=None):
         self._name = "ThroughputNormalizedByCostSum_Perf"
         self._policy = ThroughputNormalizedByCostSumWithPerfSLOs(solver, native)
-
-    @property
-    def name(self):
-        return self._name
 
     @property
     def last_level(self):
@@ -121,16 +92,12 @@ class ThroughputNormalizedByCostSumWithPerf:
                                            instance_costs=instance_costs)
 
 
-class ThroughputSumWithPerf:
+class ThroughputSumWithPerf(Policy):
     """max_sum_throughput.py:11-20."""
 
     def __init__(self, solver=None, native=None):
         self._name = "ThroughputSumWithPerf"
         self._policy = ThroughputNormalizedByCostSumWithPerfSLOs(solver, native)
-
-    @property
-    def name(self):
-        return self._name
 
     @property
     def last_level(self):

@@ -30,23 +30,11 @@ zero: with x ≥ 0 the LP's row is the same.  The result is clipped to [0, 1]
 """
 import numpy as np
 
-import sw_native
+from sw_policy import Policy, clipped, identical_types, int_workers, split_over_types, with_v100_throughputs
+from sw_policy import flatten as _flatten, unflatten as _unflatten
 
 
-def _flatten(d, cluster_spec):
-    """policy.py:28-44: jobs sorted by id, worker types sorted by name (from
-    the first job), the throughput matrix."""
-    job_ids = sorted(d.keys())
-    if len(job_ids) == 0:
-        return None, None
-    worker_types = sorted(d[job_ids[0]].keys())
-    if len(worker_types) == 0:
-        return None, None
-    m = np.array([[d[j][wt] for wt in worker_types] for j in job_ids], dtype=np.float64)
-    return m, (job_ids, worker_types)
-
-
-class MinTotalDurationPolicyWithPerf:
+class MinTotalDurationPolicyWithPerf(Policy):
     """min_total_duration.py:41-106."""
 
     def __init__(self, solver=None, native=None, worker_types=False):
@@ -56,22 +44,13 @@ class MinTotalDurationPolicyWithPerf:
         self._worker_types = worker_types  # throughputs that differ by type: sw_mtd_allocate_types
         self.last_level = None  # (T, μ) of the last solve; (T, t*, flags) of one over differing types
 
-    @property
-    def name(self):
-        return self._name
-
-    def _engine(self):
-        if self._native is None:
-            self._native = sw_native.Solver(device=0)
-        return self._native
-
     def get_allocation(self, unflattened_throughputs, scale_factors, num_steps_remaining, cluster_spec):
-        throughputs, index = _flatten(unflattened_throughputs, cluster_spec)
+        throughputs, index = _flatten(unflattened_throughputs)
         if throughputs is None:
             return None
-        m, n = throughputs.shape
+        m = len(throughputs)
         job_ids, worker_types = index
-        if not (throughputs == throughputs[:, :1]).all():
+        if not identical_types(throughputs):
             if not self._worker_types:
                 raise NotImplementedError(
                     "MinTotalDuration with throughputs that differ by worker type needs worker_types=True: "
@@ -83,24 +62,19 @@ class MinTotalDurationPolicyWithPerf:
         # a remainder below zero asks for nothing: tp·x ≥ steps/T with x ≥ 0 is then the row of steps = 0
         full_time = np.array([max(num_steps_remaining[job_ids[i]], 0) / throughputs[i, 0] for i in range(m)],
                              dtype=np.float64)
-        workers = [int(cluster_spec[wt]) for wt in worker_types]
+        workers = int_workers(worker_types, cluster_spec)
         total = sum(workers)
         sf = np.array([scale_factors[j] for j in job_ids], dtype=np.int32)
         x, T, mu = self._engine().mtd_allocate(sf, full_time, total)
         self.last_level = (T, mu)
         x = np.asarray(x, dtype=np.float64)
-        if n == 1:
-            xs = x.reshape(m, 1)
-        else:
-            xs = np.array([[x[i] * workers[k] / total for k in range(n)] for i in range(m)])
-        xs = xs.clip(min=0.0).clip(max=1.0)
-        return {job_ids[i]: {worker_types[k]: xs[i, k] for k in range(n)} for i in range(m)}
-
+        xs = split_over_types(x, workers, total)
+        return _unflatten(clipped(xs), index)
 
     def _allocation_over_types(self, throughputs, index, scale_factors, num_steps_remaining, cluster_spec):
         m, n = throughputs.shape
         job_ids, worker_types = index
-        workers = np.array([int(cluster_spec[wt]) for wt in worker_types], dtype=np.int32)
+        workers = np.array(int_workers(worker_types, cluster_spec), dtype=np.int32)
         steps = np.array([max(num_steps_remaining[j], 0) for j in job_ids], dtype=np.float64)
         for i in range(m):
             if steps[i] > 0 and not (throughputs[i, workers > 0] > 0).any():
@@ -109,11 +83,10 @@ class MinTotalDurationPolicyWithPerf:
         sf = np.array([scale_factors[j] for j in job_ids], dtype=np.int32)
         x, T, t, _, flags = self._engine().mtd_allocate_types(workers, sf, throughputs, steps)
         self.last_level = (T, t, flags)
-        xs = np.asarray(x, dtype=np.float64).reshape(m, n).clip(min=0.0).clip(max=1.0)
-        return {job_ids[i]: {worker_types[k]: xs[i, k] for k in range(n)} for i in range(m)}
+        return _unflatten(clipped(np.asarray(x, dtype=np.float64).reshape(m, n)), index)
 
 
-class MinTotalDurationPolicy:
+class MinTotalDurationPolicy(Policy):
     """min_total_duration.py:11-38: the WithPerf policy with every worker
     type's throughput replaced by the job's v100 throughput."""
 
@@ -122,21 +95,12 @@ class MinTotalDurationPolicy:
         self._min_total_duration_perf_policy = MinTotalDurationPolicyWithPerf(solver, native)
 
     @property
-    def name(self):
-        return self._name
-
-    @property
     def last_level(self):
         return self._min_total_duration_perf_policy.last_level
 
     def get_allocation(self, unflattened_throughputs, scale_factors, num_steps_remaining, cluster_spec):
-        throughputs, _ = _flatten(unflattened_throughputs, cluster_spec)
+        throughputs, _ = _flatten(unflattened_throughputs)
         if throughputs is None:
             return None
-        new_unflattened_throughputs = {}
-        for job_id in unflattened_throughputs:
-            new_unflattened_throughputs[job_id] = {}
-            for worker_type in unflattened_throughputs[job_id]:
-                new_unflattened_throughputs[job_id][worker_type] = unflattened_throughputs[job_id]["v100"]
         return self._min_total_duration_perf_policy.get_allocation(
-            new_unflattened_throughputs, scale_factors, num_steps_remaining, cluster_spec)
+            with_v100_throughputs(unflattened_throughputs), scale_factors, num_steps_remaining, cluster_spec)

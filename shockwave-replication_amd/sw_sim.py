@@ -50,17 +50,25 @@ the product solvers (HIP, default) or with the CPU oracles (tests only):
 from __future__ import annotations
 
 import heapq
+import importlib
 import math
+import time
 from collections import OrderedDict
 
-try:
-    from . import sw_trace as st
-    from .job_metadata import ShockwaveJobMetadata
-    from .shockwave import ShockwaveScheduler
-except ImportError:  # flat-module use
-    import sw_trace as st
-    from job_metadata import ShockwaveJobMetadata
-    from shockwave import ShockwaveScheduler
+
+def _sibling(name):
+    """The module of this directory: of the package when imported as one, else flat."""
+    if __package__:
+        try:
+            return importlib.import_module("." + name, __package__)
+        except ImportError:
+            pass
+    return importlib.import_module(name)
+
+
+st = _sibling("sw_trace")
+ShockwaveJobMetadata = _sibling("job_metadata").ShockwaveJobMetadata
+ShockwaveScheduler = _sibling("shockwave").ShockwaveScheduler
 
 BS_BIG = 0  # scheduler.py:61-62
 BS_SMALL = 1
@@ -74,6 +82,29 @@ POLICY_NAMES = {"shockwave": "Shockwave", "max_min_fairness": "MaxMinFairness",
                 "max_sum_throughput_perf": "ThroughputSumWithPerf",
                 "allox": "AlloX_Perf"}
 ALLOX_ALPHA_PREFIX = "allox_alpha="  # utils.get_policy :485-490
+
+# policy name → the mirror's module and class, the Simulator attribute that holds its
+# engine, its constructor's keywords (→ the Simulator attribute of each) and the per-job
+# dictionaries of the allocation state that get_allocation takes before the cluster
+MIRRORS = {
+    "FinishTimeFairness": ("finish_time_fairness", "FinishTimeFairnessPolicy", "_ftf_allocator", {},
+                           ("throughputs", "scale_factors", "priority_weights", "times_since_start",
+                            "num_steps_remaining")),
+    "MinTotalDuration": ("min_total_duration", "MinTotalDurationPolicy", "_mtd_allocator", {},
+                         ("throughputs", "scale_factors", "num_steps_remaining")),
+    "ThroughputSumWithPerf": ("max_sum_throughput", "ThroughputSumWithPerf", "_mst_allocator", {},
+                              ("throughputs", "scale_factors")),
+    "AlloX_Perf": ("allox", "AlloXPolicy", "_allox_allocator", {"alpha": "_allox_alpha"},
+                   ("throughputs", "scale_factors", "times_since_start", "num_steps_remaining")),
+}
+# one job's entry of each dictionary (scheduler.py:2351-2428, _get_allocation_state)
+JOB_STATE = {
+    "throughputs": lambda sim, j: {WORKER_TYPE: sim._throughputs[j]},
+    "scale_factors": lambda sim, j: sim._jobs[j].scale_factor,
+    "priority_weights": lambda sim, j: sim._jobs[j].priority_weight,
+    "num_steps_remaining": lambda sim, j: sim._remaining_steps(j),
+    "times_since_start": lambda sim, j: sim._current_timestamp - sim._per_job_start_timestamps[j],
+}
 
 
 def _allox_alpha(policy):
@@ -162,14 +193,11 @@ class Simulator:
             self._shockwave = None
         self._mmf_allocator = mmf_allocator
         self._ftf_allocator = ftf_allocator
-        self._ftf_policy = None
         self._wf_allocator = wf_allocator
         self._mtd_allocator = mtd_allocator
-        self._mtd_policy = None
         self._mst_allocator = mst_allocator
-        self._mst_policy = None
         self._allox_allocator = allox_allocator
-        self._allox_policy = None
+        self._mirror = None  # the policy mirror of a MIRRORS policy, built at its first allocation
 
     # ---- helpers ------------------------------------------------------------------
     def _log(self, msg):
@@ -365,7 +393,6 @@ class Simulator:
 
     def _shockwave_schedule(self):
         """scheduler.py:991-1014: the cached plan's round, filtered to active jobs."""
-        import time
         before = self._shockwave.last_solve
         t0 = time.perf_counter()
         self._current_round_scheduled_jobs = self._shockwave.current_round_schedule()
@@ -387,21 +414,14 @@ class Simulator:
         MaxMinFairnessWaterFilling (max_min_fairness_water_filling.py:412-468,
         called with the same arguments, scheduler.py:2433-2436) takes the same
         sf_j and c_j and returns x_j = min(1, L*/c_j)."""
-        if self.policy_name == "FinishTimeFairness":
-            return self._compute_ftf_allocation()
-        if self.policy_name == "MinTotalDuration":
-            return self._compute_mtd_allocation()
-        if self.policy_name == "ThroughputSumWithPerf":
-            return self._compute_mst_allocation()
-        if self.policy_name == "AlloX_Perf":
-            return self._compute_allox_allocation()
+        if self.policy_name in MIRRORS:
+            return self._compute_mirror_allocation()
         ids = sorted(self._jobs.keys())
         if not ids:
             return {}
         sf = [self._jobs[j].scale_factor for j in ids]
         coef = [self._jobs[j].scale_factor / self._jobs[j].priority_weight for j in ids]
         allocator = self._share_allocator()
-        import time
         t0 = time.perf_counter()
         x = allocator(sf, coef, len(self._worker_ids))
         self.num_solves += 1
@@ -414,125 +434,28 @@ class Simulator:
         water_filling = self.policy_name == "MaxMinFairnessWaterFilling"
         attr = "_wf_allocator" if water_filling else "_mmf_allocator"
         if getattr(self, attr) is None:
-            try:
-                from . import sw_native
-            except ImportError:
-                import sw_native
+            sw_native = _sibling("sw_native")
             setattr(self, attr, sw_native.WfAllocator() if water_filling else sw_native.MmfAllocator())
         return getattr(self, attr)
 
-    def _compute_ftf_allocation(self):
-        """scheduler.py:2351-2428 → policies/finish_time_fairness.py:14-140: the
-        allocation state (_get_allocation_state) handed to the policy mirror,
-        which keeps the reference's per-job state between calls."""
-        if self._ftf_policy is None:
-            try:
-                from . import sw_native
-                from .finish_time_fairness import FinishTimeFairnessPolicy
-            except ImportError:
-                import sw_native
-                from finish_time_fairness import FinishTimeFairnessPolicy
-            if self._ftf_allocator is None:
-                self._ftf_allocator = sw_native.Solver(device=0)
-            self._ftf_policy = FinishTimeFairnessPolicy(native=self._ftf_allocator)
-        jobs = self._jobs
-        throughputs = {j: {WORKER_TYPE: self._throughputs[j]} for j in jobs}
-        scale_factors = {j: jobs[j].scale_factor for j in jobs}
-        priority_weights = {j: jobs[j].priority_weight for j in jobs}
-        num_steps_remaining = {j: self._remaining_steps(j) for j in jobs}
-        times_since_start = {j: self._current_timestamp - self._per_job_start_timestamps[j] for j in jobs}
+    def _compute_mirror_allocation(self):
+        """scheduler.py:2351-2466 → the policy mirror of MIRRORS: the allocation
+        state (_get_allocation_state) handed to the mirror, which keeps the
+        reference's state between calls (FinishTimeFairness its per-job times,
+        AlloX the previous allocation: a job that holds a worker keeps it; it
+        asserts that every scale factor is 1).  The max-sum-throughput mirror
+        gets no SLOs and no instance costs; a job its optimum starves gets 0.0,
+        which _update_priorities turns into priority 0."""
+        module, cls, attr, keywords, names = MIRRORS[self.policy_name]
+        if self._mirror is None:
+            if getattr(self, attr) is None:
+                setattr(self, attr, _sibling("sw_native").Solver(device=0))
+            self._mirror = getattr(_sibling(module), cls)(
+                native=getattr(self, attr), **{k: getattr(self, a) for k, a in keywords.items()})
+        state = [{j: JOB_STATE[name](self, j) for j in self._jobs} for name in names]
         cluster_spec = {WORKER_TYPE: len(self._worker_ids)}
-        import time
         t0 = time.perf_counter()
-        allocation = self._ftf_policy.get_allocation(throughputs, scale_factors, priority_weights,
-                                                     times_since_start, num_steps_remaining, cluster_spec)
-        if allocation is None:
-            return {}
-        self.num_solves += 1
-        self.solve_seconds += time.perf_counter() - t0
-        return {j: float(allocation[j][WORKER_TYPE]) for j in allocation}
-
-    def _compute_mtd_allocation(self):
-        """scheduler.py:2351-2440 → policies/min_total_duration.py:11-106: the
-        allocation state of the FinishTimeFairness branch less the times."""
-        if self._mtd_policy is None:
-            try:
-                from . import sw_native
-                from .min_total_duration import MinTotalDurationPolicy
-            except ImportError:
-                import sw_native
-                from min_total_duration import MinTotalDurationPolicy
-            if self._mtd_allocator is None:
-                self._mtd_allocator = sw_native.Solver(device=0)
-            self._mtd_policy = MinTotalDurationPolicy(native=self._mtd_allocator)
-        jobs = self._jobs
-        throughputs = {j: {WORKER_TYPE: self._throughputs[j]} for j in jobs}
-        scale_factors = {j: jobs[j].scale_factor for j in jobs}
-        num_steps_remaining = {j: self._remaining_steps(j) for j in jobs}
-        cluster_spec = {WORKER_TYPE: len(self._worker_ids)}
-        import time
-        t0 = time.perf_counter()
-        allocation = self._mtd_policy.get_allocation(throughputs, scale_factors, num_steps_remaining,
-                                                     cluster_spec)
-        if allocation is None:
-            return {}
-        self.num_solves += 1
-        self.solve_seconds += time.perf_counter() - t0
-        return {j: float(allocation[j][WORKER_TYPE]) for j in allocation}
-
-    def _compute_mst_allocation(self):
-        """scheduler.py:2351-2411, :2460-2463 → policies/max_sum_throughput.py:11-96:
-        throughputs, scale factors and the cluster, no SLOs and no instance
-        costs.  A job the optimum starves gets 0.0, which _update_priorities
-        turns into priority 0."""
-        if self._mst_policy is None:
-            try:
-                from . import sw_native
-                from .max_sum_throughput import ThroughputSumWithPerf
-            except ImportError:
-                import sw_native
-                from max_sum_throughput import ThroughputSumWithPerf
-            if self._mst_allocator is None:
-                self._mst_allocator = sw_native.Solver(device=0)
-            self._mst_policy = ThroughputSumWithPerf(native=self._mst_allocator)
-        jobs = self._jobs
-        throughputs = {j: {WORKER_TYPE: self._throughputs[j]} for j in jobs}
-        scale_factors = {j: jobs[j].scale_factor for j in jobs}
-        cluster_spec = {WORKER_TYPE: len(self._worker_ids)}
-        import time
-        t0 = time.perf_counter()
-        allocation = self._mst_policy.get_allocation(throughputs, scale_factors, cluster_spec)
-        if allocation is None:
-            return {}
-        self.num_solves += 1
-        self.solve_seconds += time.perf_counter() - t0
-        return {j: float(allocation[j][WORKER_TYPE]) for j in allocation}
-
-    def _compute_allox_allocation(self):
-        """scheduler.py:2351-2419 → policies/allox.py:13-141: the allocation
-        state of the FinishTimeFairness branch less the priority weights.  The
-        mirror keeps the previous allocation between calls (a job that holds a
-        worker keeps it) and asserts that every scale factor is 1."""
-        if self._allox_policy is None:
-            try:
-                from . import sw_native
-                from .allox import AlloXPolicy
-            except ImportError:
-                import sw_native
-                from allox import AlloXPolicy
-            if self._allox_allocator is None:
-                self._allox_allocator = sw_native.Solver(device=0)
-            self._allox_policy = AlloXPolicy(alpha=self._allox_alpha, native=self._allox_allocator)
-        jobs = self._jobs
-        throughputs = {j: {WORKER_TYPE: self._throughputs[j]} for j in jobs}
-        scale_factors = {j: jobs[j].scale_factor for j in jobs}
-        num_steps_remaining = {j: self._remaining_steps(j) for j in jobs}
-        times_since_start = {j: self._current_timestamp - self._per_job_start_timestamps[j] for j in jobs}
-        cluster_spec = {WORKER_TYPE: len(self._worker_ids)}
-        import time
-        t0 = time.perf_counter()
-        allocation = self._allox_policy.get_allocation(throughputs, scale_factors, times_since_start,
-                                                       num_steps_remaining, cluster_spec)
+        allocation = self._mirror.get_allocation(*state, cluster_spec)
         if allocation is None:
             return {}
         self.num_solves += 1

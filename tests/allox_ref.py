@@ -14,34 +14,26 @@ Only tests/ (and tools/ run by hand) may import this module.
 """
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 from scipy.optimize import linear_sum_assignment
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(os.path.dirname(_HERE), "shockwave-replication_amd", "csrc")
-_SO = os.path.join(os.path.dirname(_HERE), "shockwave-replication_amd", "lib", "liballox_twin.so")
-_LIB = None
+import twinlib
 
 MAX_JOBS = 1024
 MAX_WORKERS = 1024
 DENSE_CAP = 4_000_000  # entries of the dense matrix the tests hand to scipy
 
 
+def _declare(lib):
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    lib.allox_twin_assign.argtypes = [C.c_int32, C.c_int32, ip, dp, dp, ip, ip, ip, dp, C.c_void_p,
+                                      C.POINTER(C.c_int64)]
+    lib.allox_twin_assign.restype = C.c_int
+
+
 def _lib():
-    global _LIB
-    if _LIB is None:
-        if not os.path.exists(_SO):
-            subprocess.check_call(["make", "-s", "-C", _CSRC, "../lib/liballox_twin.so"])
-        lib = C.CDLL(_SO)
-        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-        lib.allox_twin_assign.argtypes = [C.c_int32, C.c_int32, ip, dp, dp, ip, ip, ip, dp, C.c_void_p,
-                                          C.POINTER(C.c_int64)]
-        lib.allox_twin_assign.restype = C.c_int
-        _LIB = lib
-    return _LIB
+    return twinlib.load("liballox_twin.so", _declare, built_by="csrc")
 
 
 def arrays(free_workers, proc_time, delay):

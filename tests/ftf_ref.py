@@ -16,30 +16,22 @@ Only tests/ may import this module.
 """
 import ctypes as C
 import math
-import os
-import subprocess
 from fractions import Fraction
 
 import numpy as np
 from scipy.optimize import minimize
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(os.path.dirname(_HERE), "shockwave-replication_amd", "csrc")
-_SO = os.path.join(os.path.dirname(_HERE), "shockwave-replication_amd", "lib", "libftf_twin.so")
-_LIB = None
+import twinlib
+
+
+def _declare(lib):
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    lib.ftf_twin_allocate.argtypes = [C.c_int32, C.c_int32, ip, dp, dp, dp, dp, dp, dp]
+    lib.ftf_twin_allocate.restype = C.c_int
 
 
 def _lib():
-    global _LIB
-    if _LIB is None:
-        if not os.path.exists(_SO):
-            subprocess.check_call(["make", "-s", "-C", _CSRC, "../lib/libftf_twin.so"])
-        lib = C.CDLL(_SO)
-        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-        lib.ftf_twin_allocate.argtypes = [C.c_int32, C.c_int32, ip, dp, dp, dp, dp, dp, dp]
-        lib.ftf_twin_allocate.restype = C.c_int
-        _LIB = lib
-    return _LIB
+    return twinlib.load("libftf_twin.so", _declare, built_by="csrc")
 
 
 def twin_allocate(scale_factors, full_time, elapsed, isolated_time, num_workers):

@@ -6,36 +6,27 @@ families of tests/test_ftf_types.py and tests/test_gpu_ftf_types.py, and the
 references computed once and shared.  Only tests/ may import this module."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 
 import ftf_types_ref as ref
 import mtdtcases as mt
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(os.path.dirname(_HERE), "shockwave-replication_amd", "csrc")
-_SO = os.path.join(os.path.dirname(_HERE), "shockwave-replication_amd", "lib", "libftft_twin.so")
-_LIB = None
+import twinlib
 
 FAMILIES = mt.FAMILIES
 
 
+def _declare(lib):
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    lib.ftft_twin_allocate.argtypes = [C.c_int32, C.c_int32, ip, ip, dp, dp, dp, dp, dp, dp]
+    lib.ftft_twin_allocate.restype = C.c_int
+    lib.ftft_twin_tol.restype = C.c_double
+    for f in ("max_solves", "max_jobs", "max_types", "flag_box", "flag_idle", "flag_safe", "status_cap"):
+        getattr(lib, "ftft_twin_" + f).restype = C.c_int32
+
+
 def _lib():
-    global _LIB
-    if _LIB is None:
-        if not os.path.exists(_SO):
-            subprocess.check_call(["make", "-s", "-C", _CSRC, "../lib/libftft_twin.so"])
-        lib = C.CDLL(_SO)
-        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-        lib.ftft_twin_allocate.argtypes = [C.c_int32, C.c_int32, ip, ip, dp, dp, dp, dp, dp, dp]
-        lib.ftft_twin_allocate.restype = C.c_int
-        lib.ftft_twin_tol.restype = C.c_double
-        for f in ("max_solves", "max_jobs", "max_types", "flag_box", "flag_idle", "flag_safe", "status_cap"):
-            getattr(lib, "ftft_twin_" + f).restype = C.c_int32
-        _LIB = lib
-    return _LIB
+    return twinlib.load("libftft_twin.so", _declare, built_by="csrc")
 
 
 def const(name):

@@ -6,35 +6,26 @@ families of tests/test_mmf_centre.py and tests/test_gpu_mmf_centre.py, and the
 references computed once and shared.  Only tests/ may import this module."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 
 import mmf_centre_ref
 import mmf_ref
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(os.path.dirname(_HERE), "shockwave-replication_amd", "csrc")
-_SO = os.path.join(os.path.dirname(_HERE), "shockwave-replication_amd", "lib", "libmmfc_twin.so")
-_LIB = None
+import twinlib
 
 FAMILIES = ("generic", "identical", "integer")
 
 
+def _declare(lib):
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    lib.mmfc_twin_allocate.argtypes = [C.c_int32, C.c_int32, ip, ip, dp, dp, dp]
+    lib.mmfc_twin_allocate.restype = C.c_int
+    lib.mmfc_twin_max_iters.restype = C.c_int32
+    lib.mmfc_twin_max_jobs.restype = C.c_int32
+
+
 def _lib():
-    global _LIB
-    if _LIB is None:
-        if not os.path.exists(_SO):
-            subprocess.check_call(["make", "-s", "-C", _CSRC, "../lib/libmmfc_twin.so"])
-        lib = C.CDLL(_SO)
-        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-        lib.mmfc_twin_allocate.argtypes = [C.c_int32, C.c_int32, ip, ip, dp, dp, dp]
-        lib.mmfc_twin_allocate.restype = C.c_int
-        lib.mmfc_twin_max_iters.restype = C.c_int32
-        lib.mmfc_twin_max_jobs.restype = C.c_int32
-        _LIB = lib
-    return _LIB
+    return twinlib.load("libmmfc_twin.so", _declare, built_by="csrc")
 
 
 def twin_allocate_rc(workers, scale_factors, coefficients):

@@ -6,38 +6,29 @@ families of tests/test_mtd_types.py and tests/test_gpu_mtd_types.py, and the
 references computed once and shared.  Only tests/ may import this module."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 
 import mmfccases as mc
 import mtd_types_ref as ref
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(os.path.dirname(_HERE), "shockwave-replication_amd", "csrc")
-_SO = os.path.join(os.path.dirname(_HERE), "shockwave-replication_amd", "lib", "libmtdt_twin.so")
-_LIB = None
+import twinlib
 
 FAMILIES = ("narrow", "wide")
 FIRST_PROBE = 500050.0  # (100 + 1e6)/2
 
 
+def _declare(lib):
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    lib.mtdt_twin_allocate.argtypes = [C.c_int32, C.c_int32, ip, ip, dp, dp, dp, dp]
+    lib.mtdt_twin_allocate.restype = C.c_int
+    for f in ("thin", "full_time_max"):
+        getattr(lib, "mtdt_twin_" + f).restype = C.c_double
+    for f in ("max_iters", "max_jobs", "max_types", "flag_idle", "flag_thin"):
+        getattr(lib, "mtdt_twin_" + f).restype = C.c_int32
+
+
 def _lib():
-    global _LIB
-    if _LIB is None:
-        if not os.path.exists(_SO):
-            subprocess.check_call(["make", "-s", "-C", _CSRC, "../lib/libmtdt_twin.so"])
-        lib = C.CDLL(_SO)
-        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-        lib.mtdt_twin_allocate.argtypes = [C.c_int32, C.c_int32, ip, ip, dp, dp, dp, dp]
-        lib.mtdt_twin_allocate.restype = C.c_int
-        for f in ("thin", "full_time_max"):
-            getattr(lib, "mtdt_twin_" + f).restype = C.c_double
-        for f in ("max_iters", "max_jobs", "max_types", "flag_idle", "flag_thin"):
-            getattr(lib, "mtdt_twin_" + f).restype = C.c_int32
-        _LIB = lib
-    return _LIB
+    return twinlib.load("libmtdt_twin.so", _declare, built_by="csrc")
 
 
 def const(name):

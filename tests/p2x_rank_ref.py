@@ -13,16 +13,13 @@ A placement is the dict of tests/p2xcases.py (T, G, job, w, c, m); a candidate
 is a list of jobs (or None).  Only tests/ may import this module.
 """
 import ctypes as C
-import os
 import struct
 
 import numpy as np
 
-KMAX, TMAX, AMAX, NT, MAX_MOVES, HDR_INTS = 8, 64, 4096, 512, 1024, 48
+import twinlib
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SO = os.path.join(os.path.dirname(_HERE), "shockwave-replication_amd", "lib", "libp2x_rank_probe.so")
-_LIB = None
+KMAX, TMAX, AMAX, NT, MAX_MOVES, HDR_INTS = 8, 64, 4096, 512, 1024, 48
 
 
 def bits(x):
@@ -94,20 +91,19 @@ def predict_ranked(P, cand, njobs):
     return int(partition(P, cand) == rank_order(P))
 
 
+def _declare(lib):
+    dp, ip, up, lp, wp = (C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint64),
+                          C.POINTER(C.c_int64), C.POINTER(C.c_uint32))
+    lib.p2x_rank_probe_setup.argtypes = [C.c_int32, lp, ip, ip, ip, ip, dp, up, wp, ip, ip, lp, ip, ip, dp, up,
+                                         ip, dp, ip]
+    lib.p2x_rank_probe_run.argtypes = [C.c_int32, lp, ip, ip, ip, ip, dp, up, wp, ip, ip, ip]
+    lib.p2x_rank_probe_setup.restype = C.c_int
+    lib.p2x_rank_probe_run.restype = C.c_int
+
+
 def _lib():
     """libp2x_rank_probe.so; absent means the build is broken (no fall-back)."""
-    global _LIB
-    if _LIB is None:
-        lib = C.CDLL(_SO)
-        dp, ip, up, lp, wp = (C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint64),
-                              C.POINTER(C.c_int64), C.POINTER(C.c_uint32))
-        lib.p2x_rank_probe_setup.argtypes = [C.c_int32, lp, ip, ip, ip, ip, dp, up, wp, ip, ip, lp, ip, ip, dp, up,
-                                             ip, dp, ip]
-        lib.p2x_rank_probe_run.argtypes = [C.c_int32, lp, ip, ip, ip, ip, dp, up, wp, ip, ip, ip]
-        lib.p2x_rank_probe_setup.restype = C.c_int
-        lib.p2x_rank_probe_run.restype = C.c_int
-        _LIB = lib
-    return _LIB
+    return twinlib.load("libp2x_rank_probe.so", _declare)
 
 
 def _p(a, t):

@@ -18,15 +18,15 @@ c = p/n and round mask (a Python int, bit t = round t).
 Only tests/ may import this module.
 """
 import ctypes as C
-import os
 import struct
-import subprocess
 from fractions import Fraction
 from math import gcd
 
 import numpy as np
 import scipy.sparse as sp
 from scipy.optimize import Bounds, LinearConstraint, milp
+
+import twinlib
 
 NONE = 1.0e300      # "no edge"
 EPS = 2e-4          # δ = ε·P2₀/T·max(1, A/128)
@@ -37,27 +37,19 @@ TMAX = 64
 AMAX = 4096
 KMAX = 8
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_ORACLE = os.path.join(os.path.dirname(_HERE), "oracle")
-_SO = os.environ.get("SW_TWIN_PATH") or os.path.join(_ORACLE, "_build", "libplan_twin.so")
-_LIB = None
+
+def _declare(lib):
+    dp, ip, up, bp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_int8)
+    lib.twin_p2x_run.argtypes = [C.c_int32, C.c_int32, C.c_int32, ip, ip, dp, up]
+    lib.twin_p2x_run.restype = C.c_int32
+    lib.twin_p2x_find_cycle.argtypes = [C.c_int32, C.c_int32, dp, ip, dp, C.c_int32, ip]
+    lib.twin_p2x_find_cycle.restype = C.c_int32
+    lib.twin_p2x_edges.argtypes = [C.c_int32, C.c_int32, C.c_int32, ip, ip, dp, up, C.c_int32, dp, bp]
+    lib.twin_p2x_edges.restype = C.c_double
 
 
 def _lib():
-    global _LIB
-    if _LIB is None:
-        if not os.path.exists(_SO):
-            subprocess.check_call(["make", "-s", "-C", _ORACLE])
-        lib = C.CDLL(_SO)
-        dp, ip, up, bp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_int8)
-        lib.twin_p2x_run.argtypes = [C.c_int32, C.c_int32, C.c_int32, ip, ip, dp, up]
-        lib.twin_p2x_run.restype = C.c_int32
-        lib.twin_p2x_find_cycle.argtypes = [C.c_int32, C.c_int32, dp, ip, dp, C.c_int32, ip]
-        lib.twin_p2x_find_cycle.restype = C.c_int32
-        lib.twin_p2x_edges.argtypes = [C.c_int32, C.c_int32, C.c_int32, ip, ip, dp, up, C.c_int32, dp, bp]
-        lib.twin_p2x_edges.restype = C.c_double
-        _LIB = lib
-    return _LIB
+    return twinlib.load("libplan_twin.so", _declare, built_by="oracle")
 
 
 def _p(a, t):
@@ -106,24 +98,19 @@ def twin_edges(T, G, job, w, c, m, F):
 
 # ---- the device code through the probe library ------------------------------
 
-_PROBE_SO = os.path.join(os.path.dirname(_HERE), "shockwave-replication_amd", "lib", "libp2x_probe.so")
-_PROBE = None
+def _declare_probe(lib):
+    dp, ip, up, bp, lp = (C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint64),
+                          C.POINTER(C.c_int8), C.POINTER(C.c_int64))
+    lib.p2x_probe_run.argtypes = [C.c_int32, lp, ip, ip, ip, ip, dp, up, ip, C.c_int32]
+    lib.p2x_probe_find_cycle.argtypes = [C.c_int32, ip, ip, dp, ip, dp, ip, ip, ip]
+    lib.p2x_probe_edges.argtypes = [C.c_int32, lp, ip, ip, ip, ip, ip, dp, up, dp, bp, dp, C.c_int32]
+    for f in (lib.p2x_probe_run, lib.p2x_probe_find_cycle, lib.p2x_probe_edges):
+        f.restype = C.c_int
 
 
 def _probe():
     """libp2x_probe.so; absent means the build is broken (no fall-back)."""
-    global _PROBE
-    if _PROBE is None:
-        lib = C.CDLL(_PROBE_SO)
-        dp, ip, up, bp, lp = (C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint64),
-                              C.POINTER(C.c_int8), C.POINTER(C.c_int64))
-        lib.p2x_probe_run.argtypes = [C.c_int32, lp, ip, ip, ip, ip, dp, up, ip, C.c_int32]
-        lib.p2x_probe_find_cycle.argtypes = [C.c_int32, ip, ip, dp, ip, dp, ip, ip, ip]
-        lib.p2x_probe_edges.argtypes = [C.c_int32, lp, ip, ip, ip, ip, ip, dp, up, dp, bp, dp, C.c_int32]
-        for f in (lib.p2x_probe_run, lib.p2x_probe_find_cycle, lib.p2x_probe_edges):
-            f.restype = C.c_int
-        _PROBE = lib
-    return _PROBE
+    return twinlib.load("libp2x_probe.so", _declare_probe)
 
 
 def _batch(placements):

@@ -19,32 +19,24 @@ placement order) and caps.
 Only tests/ may import this module.
 """
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
+
+import twinlib
 
 TMAX = 64
 PAD = -12345    # what the capacity rows hold past T: nothing may read it
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_ORACLE = os.path.join(os.path.dirname(_HERE), "oracle")
-_SO = os.environ.get("SW_TWIN_PATH") or os.path.join(_ORACLE, "_build", "libplan_twin.so")
-_LIB = None
+
+def _declare(lib):
+    ip = C.POINTER(C.c_int32)
+    lib.twin_pack_arrays_caps.argtypes = [C.c_int32, C.c_int32, C.c_int32, ip, ip, C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), ip, ip, C.c_int]
+    lib.twin_pack_arrays_caps.restype = None
 
 
 def _lib():
-    global _LIB
-    if _LIB is None:
-        if not os.path.exists(_SO):
-            subprocess.check_call(["make", "-s", "-C", _ORACLE])
-        lib = C.CDLL(_SO)
-        ip = C.POINTER(C.c_int32)
-        lib.twin_pack_arrays_caps.argtypes = [C.c_int32, C.c_int32, C.c_int32, ip, ip, C.POINTER(C.c_uint64),
-                                              C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), ip, ip, C.c_int]
-        lib.twin_pack_arrays_caps.restype = None
-        _LIB = lib
-    return _LIB
+    return twinlib.load("libplan_twin.so", _declare, built_by="oracle")
 
 
 def _p(a, t):
@@ -97,25 +89,20 @@ def positions(case):
 
 # ---- the device code through the probe library ------------------------------
 
-_PROBE_SO = os.path.join(os.path.dirname(_HERE), "shockwave-replication_amd", "lib", "libpack_probe.so")
-_PROBE = None
+def _declare_probe(lib):
+    ip, up, lp, sp = C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_int64), C.POINTER(C.c_uint32)
+    for f in (lib.pack_probe_block, lib.pack_probe_wave, lib.pack_probe_one):
+        f.argtypes = [C.c_int32, C.c_int32, lp, ip, ip, ip, ip, sp, up, sp]
+    lib.pack_probe_room.argtypes = [C.c_int32, ip, ip, ip, ip, ip, ip, ip]
+    lib.pack_probe_prims.argtypes = [C.c_int32, ip, ip, ip, C.c_int32, ip, ip, ip]
+    for f in (lib.pack_probe_block, lib.pack_probe_wave, lib.pack_probe_one, lib.pack_probe_room,
+              lib.pack_probe_prims):
+        f.restype = C.c_int
 
 
 def _probe():
     """libpack_probe.so; absent means the build is broken (no fall-back)."""
-    global _PROBE
-    if _PROBE is None:
-        lib = C.CDLL(_PROBE_SO)
-        ip, up, lp, sp = C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_int64), C.POINTER(C.c_uint32)
-        for f in (lib.pack_probe_block, lib.pack_probe_wave, lib.pack_probe_one):
-            f.argtypes = [C.c_int32, C.c_int32, lp, ip, ip, ip, ip, sp, up, sp]
-        lib.pack_probe_room.argtypes = [C.c_int32, ip, ip, ip, ip, ip, ip, ip]
-        lib.pack_probe_prims.argtypes = [C.c_int32, ip, ip, ip, C.c_int32, ip, ip, ip]
-        for f in (lib.pack_probe_block, lib.pack_probe_wave, lib.pack_probe_one, lib.pack_probe_room,
-                  lib.pack_probe_prims):
-            f.restype = C.c_int
-        _PROBE = lib
-    return _PROBE
+    return twinlib.load("libpack_probe.so", _declare_probe)
 
 
 def _rows(cases):

@@ -9,35 +9,16 @@ steps and, for one worker type, the known optimum.  It is built twice —
 plain, and with the address and undefined-behaviour sanitizers — as a
 stand-alone host program.
 """
-import os
-import shutil
-import subprocess
+from nativecheck import SANITIZE, build_and_run
 
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "native", "allox_check.c")
-
-
-def _build_and_run(tmp_path, name, extra):
-    cc = shutil.which("gcc")
-    assert cc, "no host C compiler (gcc)"
-    exe = str(tmp_path / name)
-    subprocess.check_call([cc, "-std=c99", "-O2", "-Wall", "-Wextra", "-Werror", "-Wno-unused-function",
-                           "-ffp-contract=off", *extra, "-o", exe, SRC, "-lm"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert r.stdout.startswith("ok "), r.stdout + r.stderr
-    return int(r.stdout.split()[1])
+SRC = "allox_check.c"  # in tests/native/
+FLAGS = ["-ffp-contract=off"]
 
 
 def test_allox_twin_properties(tmp_path):
-    assert _build_and_run(tmp_path, "allox_check", []) > 50_000
+    assert build_and_run(tmp_path, SRC, "allox_check", "c", FLAGS) > 50_000
 
 
 def test_allox_twin_under_sanitizers(tmp_path):
-    checks = _build_and_run(tmp_path, "allox_check_san",
-                            ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                             # the runtimes inside the program: it must start whatever else the
-                             # environment loads into it first
-                             "-static-libasan", "-static-libubsan"])
+    checks = build_and_run(tmp_path, SRC, "allox_check_san", "c", FLAGS + SANITIZE)
     assert checks > 50_000

@@ -13,36 +13,17 @@ call succeeds and every row of the program holds at the returned ρ.  It is
 built twice — plain, and with the address and undefined-behaviour sanitizers —
 as a stand-alone host program.
 """
-import os
-import shutil
-import subprocess
+from nativecheck import SANITIZE, build_and_run
 
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "native", "ftft_check.c")
-
-
-def _build_and_run(tmp_path, name, extra, reps):
-    cc = shutil.which("gcc")
-    assert cc, "no host C compiler (gcc)"
-    exe = str(tmp_path / name)
-    subprocess.check_call([cc, "-std=c99", "-O2", "-Wall", "-Wextra", "-Werror", "-Wno-unused-function",
-                           "-ffp-contract=off", "-fno-fast-math", *extra, "-o", exe, SRC, "-lm"])
-    r = subprocess.run([exe, str(reps)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert r.stdout.startswith("ok "), r.stdout + r.stderr
-    return int(r.stdout.split()[1])
+SRC = "ftft_check.c"  # in tests/native/
+FLAGS = ["-ffp-contract=off", "-fno-fast-math"]
 
 
 def test_ftf_types_header_ladder(tmp_path):
-    checks = _build_and_run(tmp_path, "ftft_check", [], 2)
+    checks = build_and_run(tmp_path, SRC, "ftft_check", "c", FLAGS, [2], timeout=300)
     assert checks > 100_000
 
 
 def test_ftf_types_header_under_sanitizers(tmp_path):
-    checks = _build_and_run(tmp_path, "ftft_check_san",
-                            ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                             # the runtimes inside the program: it must start whatever else the
-                             # environment loads into it first
-                             "-static-libasan", "-static-libubsan"], 1)
+    checks = build_and_run(tmp_path, SRC, "ftft_check_san", "c", FLAGS + SANITIZE, [1], timeout=300)
     assert checks > 50_000

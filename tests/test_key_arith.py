@@ -12,39 +12,19 @@ cannot pass the validator and is left out; the program's header lists what
 else is and why.  It is built twice — plain, and with the address and
 undefined-behaviour sanitizers — as a stand-alone host program.
 """
-import os
-import shutil
-import subprocess
+from nativecheck import CSRC, SANITIZE, build_and_run
 
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "native", "key_arith_check.cpp")
-CSRC = os.path.join(ROOT, "shockwave-replication_amd", "csrc")
-
-
-def _build_and_run(tmp_path, name, extra, count):
-    cxx = shutil.which("g++")
-    assert cxx, "no host C++ compiler (g++)"
-    exe = str(tmp_path / name)
-    # the twin's floating-point flags: no contraction, no fast-math
-    subprocess.check_call([cxx, "-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off",
-                           "-fno-fast-math", "-I", CSRC, *extra, "-o", exe, SRC])
-    r = subprocess.run([exe, str(count)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert r.stdout.startswith("ok "), r.stdout + r.stderr
-    return int(r.stdout.split()[1])
+SRC = "key_arith_check.cpp"  # in tests/native/
+# the twin's floating-point flags: no contraction, no fast-math
+FLAGS = ["-ffp-contract=off", "-fno-fast-math", "-I", CSRC]
 
 
 def test_key_forms_match_twin_text(tmp_path):
     # 10 checks per random case and 4 per key of a row: a few million random values
-    checks = _build_and_run(tmp_path, "key_arith_check", [], 1_000_000)
+    checks = build_and_run(tmp_path, SRC, "key_arith_check", "c++", FLAGS, [1_000_000])
     assert checks > 10_000_000
 
 
 def test_key_forms_under_sanitizers(tmp_path):
-    checks = _build_and_run(tmp_path, "key_arith_check_san",
-                            ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                             # the runtimes inside the program: it must start whatever else the
-                             # environment loads into it first
-                             "-static-libasan", "-static-libubsan"], 200_000)
+    checks = build_and_run(tmp_path, SRC, "key_arith_check_san", "c++", FLAGS + SANITIZE, [200_000])
     assert checks > 2_000_000

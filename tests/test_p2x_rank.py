@@ -12,43 +12,24 @@
     density pack's order partitioned by class is the exchange step's rank
     order.
 """
-import os
-import shutil
-import subprocess
+from nativecheck import CSRC, SANITIZE, build_and_run
 
 import numpy as np
 
 import p2x_rank_ref as rr
 import sw_synth as ss
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "native", "p2x_rank_check.cpp")
-CSRC = os.path.join(ROOT, "shockwave-replication_amd", "csrc")
-
-
-def _build_and_run(tmp_path, name, extra, nrandom):
-    cxx = shutil.which("g++")
-    assert cxx, "no host C++ compiler (g++)"
-    exe = str(tmp_path / name)
-    subprocess.check_call([cxx, "-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off",
-                           "-I", CSRC, *extra, "-o", exe, SRC])
-    r = subprocess.run([exe, str(nrandom)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert r.stdout.startswith("ok "), r.stdout + r.stderr
-    return int(r.stdout.split()[1])
+SRC = "p2x_rank_check.cpp"  # in tests/native/
+FLAGS = ["-ffp-contract=off", "-I", CSRC]
 
 
 def test_rank_from_candidate_matches_sort(tmp_path):
-    checks = _build_and_run(tmp_path, "p2x_rank_check", [], 200)
+    checks = build_and_run(tmp_path, SRC, "p2x_rank_check", "c++", FLAGS, [200])
     assert checks > 2_000_000
 
 
 def test_rank_from_candidate_under_sanitizers(tmp_path):
-    checks = _build_and_run(tmp_path, "p2x_rank_check_san",
-                            ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                             # the runtimes inside the program: it must start whatever else the
-                             # environment loads into it first
-                             "-static-libasan", "-static-libubsan"], 60)
+    checks = build_and_run(tmp_path, SRC, "p2x_rank_check_san", "c++", FLAGS + SANITIZE, [60])
     assert checks > 1_000_000
 
 

@@ -21,33 +21,24 @@ and modes (0 fairness, 1 fifo), workers.
 Only tests/ may import this module.
 """
 import ctypes as C
-import os
-import subprocess
 from fractions import Fraction
 
 import numpy as np
 
 from wf_ref import _bottleneck_milp, _stage_lp
+import twinlib
 
 FAIRNESS, FIFO = 0, 1
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(os.path.dirname(_HERE), "shockwave-replication_amd", "csrc")
-_SO = os.path.join(os.path.dirname(_HERE), "shockwave-replication_amd", "lib", "libwfh_twin.so")
-_LIB = None
+
+def _declare(lib):
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    lib.wfh_twin_allocate.argtypes = [C.c_int32, C.c_int32, C.c_int32, ip, dp, ip, dp, ip, dp, dp, dp]
+    lib.wfh_twin_allocate.restype = C.c_int
 
 
 def _lib():
-    global _LIB
-    if _LIB is None:
-        if not os.path.exists(_SO):
-            subprocess.check_call(["make", "-s", "-C", _CSRC, "../lib/libwfh_twin.so"])
-        lib = C.CDLL(_SO)
-        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-        lib.wfh_twin_allocate.argtypes = [C.c_int32, C.c_int32, C.c_int32, ip, dp, ip, dp, ip, dp, dp, dp]
-        lib.wfh_twin_allocate.restype = C.c_int
-        _LIB = lib
-    return _LIB
+    return twinlib.load("libwfh_twin.so", _declare, built_by="csrc")
 
 
 def twin_allocate(scale_factors, coefficients, entity_of_job, entity_weights, entity_modes, num_workers):

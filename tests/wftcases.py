@@ -6,36 +6,27 @@ families of tests/test_wf_types.py and tests/test_gpu_wf_types.py, and the
 references computed once and shared.  Only tests/ may import this module."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 
 import wf_types_ref as ref
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(os.path.dirname(_HERE), "shockwave-replication_amd", "csrc")
-_SO = os.path.join(os.path.dirname(_HERE), "shockwave-replication_amd", "lib", "libwft_twin.so")
-_LIB = None
+import twinlib
 
 AMBIGUOUS_CAP = 0.02  # of a family's instances
 
 
+def _declare(lib):
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    lib.wft_twin_allocate_stats.argtypes = [C.c_int32, C.c_int32, ip, ip, dp, dp, dp, dp, ip, dp, C.c_int32]
+    lib.wft_twin_allocate_stats.restype = C.c_int
+    for f in ("thresh", "gap_lo", "gap_hi"):
+        getattr(lib, "wft_twin_" + f).restype = C.c_double
+    for f in ("max_jobs", "max_types", "flag_one", "flag_near", "flag_coarse", "status_stall"):
+        getattr(lib, "wft_twin_" + f).restype = C.c_int32
+
+
 def _lib():
-    global _LIB
-    if _LIB is None:
-        if not os.path.exists(_SO):
-            subprocess.check_call(["make", "-s", "-C", _CSRC, "../lib/libwft_twin.so"])
-        lib = C.CDLL(_SO)
-        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-        lib.wft_twin_allocate_stats.argtypes = [C.c_int32, C.c_int32, ip, ip, dp, dp, dp, dp, ip, dp, C.c_int32]
-        lib.wft_twin_allocate_stats.restype = C.c_int
-        for f in ("thresh", "gap_lo", "gap_hi"):
-            getattr(lib, "wft_twin_" + f).restype = C.c_double
-        for f in ("max_jobs", "max_types", "flag_one", "flag_near", "flag_coarse", "status_stall"):
-            getattr(lib, "wft_twin_" + f).restype = C.c_int32
-        _LIB = lib
-    return _LIB
+    return twinlib.load("libwft_twin.so", _declare, built_by="csrc")
 
 
 def const(name):
