@@ -774,6 +774,52 @@ int sw_wf_allocate_types_batch(sw_handle* h, int32_t count, int32_t num_types, c
                                double* allocation, double* levels, double* results);
 
 /*
+ * The Gavel max-sum-throughput baseline over worker types whose throughputs or
+ * instance costs DIFFER (policies/max_sum_throughput.py:39-96 without SLOs;
+ * sw_mst_allocate is the one-type program): with weights [num_jobs][num_types],
+ * w_jk = throughput_jk / cost_k,
+ *     maximise Σ_jk w_jk·x_jk   s.t.  Σ_k x_jk ≤ 1,
+ *                                     Σ_j scale_factor_j·x_jk ≤ workers_k,  x ≥ 0,
+ * in one launch (csrc/sw_mst_types.h, sw_mst_types.hip).
+ *   With y_jk = scale_factor_j·x_jk the LP is a transportation problem with
+ * integer supplies and capacities.  The call solves it EXACTLY, in integers, by
+ * successive best paths: jobs enter in index order and push their units along
+ * the best chain of displacements on a graph of the at most 17 sinks.  The
+ * allocation x_jk = y_jk / scale_factor_j is a VERTEX of the LP.  Generic
+ * weights have one optimum; with ties among differing types ECOS returns a
+ * point inside the optimal face and this call the vertex of its tie rules
+ * (lowest job, then lowest type; the unallocated remainder wins ties with a
+ * type), at the same objective.
+ *   prices[num_types] are the duals of the capacity rows: with
+ * d_jk = w_jk / scale_factor_j and
+ *     D = Σ_k workers_k·prices_k + Σ_j scale_factor_j·max(0, max_k (d_jk − prices_k)),
+ * D equals the objective up to rounding, the optimality certificate that
+ * tests/test_mst_types.py recomputes (largest gap measured: 2 ulps of the
+ * objective).  A type without workers gets shares of exactly 0.0 and the price
+ * max_j d_jk.
+ *   result[4] = the objective Σ w·x, the number of augmentations, the number of
+ * rows of the sink graph recomputed from all jobs, flags: 1 = some unit stayed
+ * unallocated, 2 = no type with workers is saturated.
+ *   SW_ERR_INVALID: a scale factor outside [1, 255], a negative worker count,
+ * a weight that is negative, not finite or above 1e30, num_types outside
+ * [1, 16], num_jobs above 16384.  SW_ERR_CAPACITY: more than
+ * 256·(num_jobs + num_types) augmentations (Σ scale_factor bounds them: a
+ * guard).
+ * num_jobs = 0 is a no-op with result and prices 0.  prices and result may be
+ * null.
+ *   The batch form takes `count` instances over one num_types in the CSR
+ * convention of sw_mtd_allocate_batch, workers and prices [count][num_types],
+ * results [count][4]; every instance's result is bit for bit that of the single
+ * call, and of the CPU twin (tests/twins/mstt_twin.c).  sw_abi_version stays 2.
+ */
+int sw_mst_allocate_types(sw_handle* h, int32_t num_jobs, int32_t num_types, const int32_t* workers,
+                          const int32_t* scale_factors, const double* weights, double* allocation,
+                          double* prices, double* result);
+int sw_mst_allocate_types_batch(sw_handle* h, int32_t count, int32_t num_types, const int64_t* offsets,
+                                const int32_t* workers, const int32_t* scale_factors, const double* weights,
+                                double* allocation, double* prices, double* results);
+
+/*
  * The Gavel max-sum-throughput baseline's allocation ("MST";
  * policies/max_sum_throughput.py:39-96, selected as max_sum_throughput_perf in
  * utils.get_policy) for one worker type.  The reference solves, with ECOS,

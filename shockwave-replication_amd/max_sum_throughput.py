@@ -18,7 +18,18 @@ The kernel solves one worker type.  Several worker types reduce to one type on
 across the types: the LP then sees only Σ_k x[j][k], and the split
 x[j][k] = x_j · workers_k / Σ workers satisfies every type's capacity.
 Throughputs or costs that differ by type are a genuine LP:
-``NotImplementedError``.  As in the reference, a job in ``SLOs`` that is
+``NotImplementedError`` unless the policy was built with ``worker_types=True``.
+Then they go to ``sw_mst_allocate_types`` (csrc/sw_mst_types.h): with
+y = scale_factor·x the LP is a transportation problem with integer supplies
+and capacities, solved exactly by successive best paths, and the allocation is
+a vertex of the LP; ``last_level`` is then (prices, augmentations, objective,
+flags).  Generic inputs have one optimum.  With ties among differing types
+ECOS returns a point inside the optimal face and the kernel the vertex of its
+tie rule (lowest job, then lowest type); the objective is the same.  Identical
+types still take the one-type path.  SLOs together with differing types still
+raise ``NotImplementedError`` (a floor on Σ_k throughput·x breaks the
+transportation structure), and an instance cost ≤ 0 raises ``ValueError``
+naming the type.  As in the reference, a job in ``SLOs`` that is
 missing from ``num_steps_remaining`` is an ``AssertionError`` and ``SLO == 0``
 a ``ZeroDivisionError``; a row with steps/SLO ≤ 0 holds for every x ≥ 0 and is
 dropped.  When the SLO rows are infeasible the reference's warning is printed
@@ -35,11 +46,14 @@ from sw_policy import flatten as _flatten, unflatten as _unflatten
 class ThroughputNormalizedByCostSumWithPerfSLOs(Policy):
     """max_sum_throughput.py:39-96."""
 
-    def __init__(self, solver=None, native=None):
+    def __init__(self, solver=None, native=None, worker_types=False):
         self._name = "ThroughputNormalizedByCostSum_PerfSLOs"
         self._solver = solver  # kept for the signature; the solve runs on the GPU
         self._native = native
-        self.last_level = None  # (λ, m, objective, slo_dropped) of the last solve
+        self._worker_types = worker_types  # throughputs or costs that differ by type: sw_mst_allocate_types
+        # (λ, m, objective, slo_dropped) of the last solve; (prices, augmentations, objective, flags) of one
+        # over differing types
+        self.last_level = None
 
     def get_allocation(self, unflattened_throughputs, scale_factors, cluster_spec, instance_costs=None,
                        SLOs={}, num_steps_remaining={}):
@@ -50,6 +64,8 @@ class ThroughputNormalizedByCostSumWithPerfSLOs(Policy):
         job_ids, worker_types = index
         costs = [1.0 if instance_costs is None else float(instance_costs[wt]) for wt in worker_types]
         if not identical_types(throughputs) or any(c != costs[0] for c in costs):
+            if self._worker_types:
+                return self._allocation_over_types(throughputs, index, costs, scale_factors, cluster_spec, SLOs)
             raise NotImplementedError(
                 "max sum throughput with throughputs or instance costs that differ by worker type is "
                 "not supported: the native kernel solves one worker type (or several identical ones)")
@@ -75,13 +91,31 @@ class ThroughputNormalizedByCostSumWithPerfSLOs(Policy):
         xs = split_over_types(x, workers, total)
         return _unflatten(clipped(xs), index)
 
+    def _allocation_over_types(self, throughputs, index, costs, scale_factors, cluster_spec, SLOs):
+        m, n = throughputs.shape
+        job_ids, worker_types = index
+        if SLOs:
+            raise NotImplementedError(
+                "max sum throughput with SLOs and throughputs or instance costs that differ by worker type is "
+                "not supported: a floor on Σ_k throughput·x breaks the transportation structure that "
+                "sw_mst_allocate_types solves")
+        for k, c in enumerate(costs):
+            if not c > 0:
+                raise ValueError(f"worker type {worker_types[k]} has instance cost {c}: costs must be > 0")
+        weights = throughputs / np.array(costs, dtype=np.float64)[None, :]
+        workers = np.array(int_workers(worker_types, cluster_spec), dtype=np.int32)
+        sf = np.array([scale_factors[j] for j in job_ids], dtype=np.int32)
+        x, prices, objective, augmentations, _, flags = self._engine().mst_allocate_types(workers, sf, weights)
+        self.last_level = (prices, augmentations, objective, flags)
+        return _unflatten(clipped(np.asarray(x, dtype=np.float64).reshape(m, n)), index)
+
 
 class ThroughputNormalizedByCostSumWithPerf(Policy):
     """max_sum_throughput.py:23-36."""
 
-    def __init__(self, solver=None, native=None):
+    def __init__(self, solver=None, native=None, worker_types=False):
         self._name = "ThroughputNormalizedByCostSum_Perf"
-        self._policy = ThroughputNormalizedByCostSumWithPerfSLOs(solver, native)
+        self._policy = ThroughputNormalizedByCostSumWithPerfSLOs(solver, native, worker_types)
 
     @property
     def last_level(self):
@@ -95,9 +129,9 @@ class ThroughputNormalizedByCostSumWithPerf(Policy):
 class ThroughputSumWithPerf(Policy):
     """max_sum_throughput.py:11-20."""
 
-    def __init__(self, solver=None, native=None):
+    def __init__(self, solver=None, native=None, worker_types=False):
         self._name = "ThroughputSumWithPerf"
-        self._policy = ThroughputNormalizedByCostSumWithPerfSLOs(solver, native)
+        self._policy = ThroughputNormalizedByCostSumWithPerfSLOs(solver, native, worker_types)
 
     @property
     def last_level(self):

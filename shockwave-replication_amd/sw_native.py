@@ -323,6 +323,7 @@ EXPORTED_SYMBOLS = (
     "sw_wfh_allocate", "sw_wfh_allocate_batch", "sw_mmf_allocate_types_centred",
     "sw_mmf_allocate_types_centred_batch", "sw_mtd_allocate_types", "sw_mtd_allocate_types_batch",
     "sw_ftf_allocate_types", "sw_ftf_allocate_types_batch", "sw_wf_allocate_types", "sw_wf_allocate_types_batch",
+    "sw_mst_allocate_types", "sw_mst_allocate_types_batch",
 )
 
 
@@ -430,6 +431,11 @@ def load(path: str | None = None):
     lib.sw_wf_allocate_types_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), _ip, _ip,
                                                _dp, _dp, _dp, _dp]
     lib.sw_wf_allocate_types_batch.restype = C.c_int
+    lib.sw_mst_allocate_types.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip, _ip, _dp, _dp, _dp, _dp]
+    lib.sw_mst_allocate_types.restype = C.c_int
+    lib.sw_mst_allocate_types_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), _ip, _ip,
+                                                _dp, _dp, _dp, _dp]
+    lib.sw_mst_allocate_types_batch.restype = C.c_int
     for name, (dtypes, _, _) in _ALLOC.items():
         cols = [_ip if t is np.int32 else _dp for t in dtypes]
         single, batch = getattr(lib, f"sw_{name}_allocate"), getattr(lib, f"sw_{name}_allocate_batch")
@@ -906,6 +912,59 @@ class Solver:
         overrides the CSR offsets built from the instances' lengths."""
         return [(x, float(l[0]), float(l[1]), float(l[2]), bool(l[3]))
                 for x, l in self._alloc_batch("mst", instances, offsets)]
+
+    # ---- max sum throughput over worker types that differ (csrc/sw_mst_types.h) ----
+    MSTT_UNPLACED = 1  # flags of mst_allocate_types: some unit stayed unallocated
+    MSTT_SLACK = 2     # no type with workers is saturated
+
+    @staticmethod
+    def _mst_types_arrays(workers, scale_factors, weights):
+        w = np.ascontiguousarray(workers, dtype=np.int32)
+        sf = np.ascontiguousarray(scale_factors, dtype=np.int32)
+        wt = np.ascontiguousarray(weights, dtype=np.float64)
+        if wt.ndim != 2 or wt.shape != (len(sf), len(w)):
+            raise ValueError("weights must be [num_jobs][num_types]")
+        return w, sf, wt
+
+    def mst_allocate_types(self, workers, scale_factors, weights):
+        """The max-sum-throughput allocation over worker types whose weights
+        (throughput / cost) differ (sw_mst_allocate_types): the exact vertex of
+        the transportation problem by successive best paths; returns (x [m, n],
+        prices [n], objective, augmentations, row recomputations, flags)."""
+        w, sf, wt = self._mst_types_arrays(workers, scale_factors, weights)
+        x = np.zeros(wt.shape, dtype=np.float64)
+        prices = np.zeros(len(w), dtype=np.float64)
+        res = np.zeros(4, dtype=np.float64)
+        self._check(self.lib.sw_mst_allocate_types(self.h, wt.shape[0], wt.shape[1],
+                                                   *map(self._ptr, (w, sf, wt, x, prices, res))),
+                    "sw_mst_allocate_types")
+        return x, prices, float(res[0]), int(res[1]), int(res[2]), int(res[3])
+
+    def mst_allocate_types_batch(self, instances, offsets=None):
+        """sw_mst_allocate_types_batch over a list of (workers, scale_factors,
+        weights) tuples with one number of types, one kernel launch; returns the
+        list of (x [m, n], prices [n], objective, augmentations, row
+        recomputations, flags).  offsets (tests only) overrides the CSR offsets
+        built from the instances."""
+        parts = [self._mst_types_arrays(*inst) for inst in instances]
+        count = len(parts)
+        n = len(parts[0][0]) if parts else 1
+        if any(len(p[0]) != n for p in parts):
+            raise ValueError("every instance must have the same number of worker types")
+        off = np.zeros(count + 1, dtype=np.int64)
+        for i, p in enumerate(parts):
+            off[i + 1] = off[i] + len(p[1])
+        cat = [np.ascontiguousarray(np.concatenate([p[c].reshape(-1) for p in parts]) if parts else [],
+                                    dtype=np.int32 if c < 2 else np.float64) for c in range(3)]
+        x = np.zeros(len(cat[2]), dtype=np.float64)
+        prices = np.zeros((count, n), dtype=np.float64)
+        res = np.zeros((count, 4), dtype=np.float64)
+        coff = off if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
+        self._check(self.lib.sw_mst_allocate_types_batch(self.h, count, n, coff.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                         *map(self._ptr, cat + [x, prices, res])),
+                    "sw_mst_allocate_types_batch")
+        return [(x[off[i] * n:off[i + 1] * n].reshape(-1, n).copy(), prices[i].copy(), float(res[i, 0]),
+                 int(res[i, 1]), int(res[i, 2]), int(res[i, 3])) for i in range(count)]
 
     # ---- AlloX assignment (include/shockwave_amd.h sw_allox_assign) ----
     @staticmethod
