@@ -11,6 +11,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
+from typing import NamedTuple
 
 import numpy as np
 
@@ -42,6 +43,15 @@ SW_NCCL_UNIQUE_ID_BYTES = 128
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
 _up = C.POINTER(C.c_uint8)
+_lp = C.POINTER(C.c_int64)
+_mp = C.POINTER(C.c_uint64)
+_POINTER = {np.dtype(t): p for t, p in ((np.float64, _dp), (np.int32, _ip), (np.uint8, _up), (np.int64, _lp),
+                                        (np.uint64, _mp))}
+
+
+def _ptr(a):
+    """The array's memory as the pointer of its dtype; None stays None (null)."""
+    return None if a is None else a.ctypes.data_as(_POINTER[a.dtype])
 
 
 class SwProblem(C.Structure):
@@ -74,7 +84,7 @@ class SwResult(C.Structure):
         ("bound", C.c_double),
         ("iters", C.c_int32),
         ("status", C.c_int32),
-        ("plan_masks", C.POINTER(C.c_uint64)),
+        ("plan_masks", _mp),
     ]
 
 
@@ -189,6 +199,12 @@ def log_bases(bases):
     return [math.log(1e-6) if b == 0.0 else math.log(b) for b in bases]
 
 
+# The six per-job columns of sw_problem: (struct field, attribute of ProblemArrays
+# and DeviceShard, pointer type).
+_JOB_COLUMNS = (("nworkers", "w", _ip), ("epoch_duration", "d", _dp), ("completed_epochs", "F", _ip),
+                ("total_epochs", "E", _ip), ("remaining_runtime", "R", _dp), ("priority", "p", _dp))
+
+
 class ProblemArrays:
     """Owns the contiguous numpy arrays behind one SwProblem (and its result).
 
@@ -227,14 +243,10 @@ class ProblemArrays:
         p.num_bases = len(self.bases)
         p.round_duration = self.delta
         p.regularizer = self.k
-        p.bases = self.bases.ctypes.data_as(_dp)
-        p.log_bases = self.ell.ctypes.data_as(_dp)
-        p.nworkers = self.w.ctypes.data_as(_ip)
-        p.epoch_duration = self.d.ctypes.data_as(_dp)
-        p.completed_epochs = self.F.ctypes.data_as(_ip)
-        p.total_epochs = self.E.ctypes.data_as(_ip)
-        p.remaining_runtime = self.R.ctypes.data_as(_dp)
-        p.priority = self.p.ctypes.data_as(_dp)
+        p.bases = _ptr(self.bases)
+        p.log_bases = _ptr(self.ell)
+        for field, attr, ptr in _JOB_COLUMNS:
+            setattr(p, field, getattr(self, attr).ctypes.data_as(ptr))
         return p
 
     def slice(self, lo: int, hi: int) -> "ProblemArrays":
@@ -245,8 +257,8 @@ class ProblemArrays:
 
     def c_result(self) -> SwResult:
         r = SwResult()
-        r.plan = self.plan.ctypes.data_as(_up)
-        r.planned_rounds = self.planned.ctypes.data_as(_ip)
+        r.plan = _ptr(self.plan)
+        r.planned_rounds = _ptr(self.planned)
         return r
 
 
@@ -259,24 +271,16 @@ class DeviceShard:
         import torch
         self.a = arrays
         dev = torch.device(device)
-        self.w = torch.from_numpy(arrays.w).to(dev)
-        self.d = torch.from_numpy(arrays.d).to(dev)
-        self.F = torch.from_numpy(arrays.F).to(dev)
-        self.E = torch.from_numpy(arrays.E).to(dev)
-        self.R = torch.from_numpy(arrays.R).to(dev)
-        self.p = torch.from_numpy(arrays.p).to(dev)
+        for _, attr, _ in _JOB_COLUMNS:
+            setattr(self, attr, torch.from_numpy(getattr(arrays, attr)).to(dev))
         self.plan = torch.zeros((arrays.N, arrays.T), dtype=torch.uint8, device=dev)
         self.planned = torch.zeros(arrays.N, dtype=torch.int32, device=dev)
         torch.cuda.synchronize(dev)  # the handle's stream does not order after torch's
 
     def c_problem(self) -> SwProblem:
         p = self.a.c_problem()  # scalars and the host bases table
-        p.nworkers = C.cast(C.c_void_p(self.w.data_ptr()), _ip)
-        p.epoch_duration = C.cast(C.c_void_p(self.d.data_ptr()), _dp)
-        p.completed_epochs = C.cast(C.c_void_p(self.F.data_ptr()), _ip)
-        p.total_epochs = C.cast(C.c_void_p(self.E.data_ptr()), _ip)
-        p.remaining_runtime = C.cast(C.c_void_p(self.R.data_ptr()), _dp)
-        p.priority = C.cast(C.c_void_p(self.p.data_ptr()), _dp)
+        for field, attr, ptr in _JOB_COLUMNS:
+            setattr(p, field, C.cast(C.c_void_p(getattr(self, attr).data_ptr()), ptr))
         return p
 
     def c_result(self) -> SwResult:
@@ -310,21 +314,90 @@ def declare_solver_api(lib, prefix: str):
     return fn
 
 
-# Every symbol include/shockwave_amd.h declares (checked by tests/test_abi.py).
-EXPORTED_SYMBOLS = (
-    "sw_abi_version", "sw_create", "sw_destroy", "sw_last_error", "sw_create_error",
-    "sw_plan_solve", "sw_plan_solve_batch", "sw_batch_upload", "sw_batch_run",
-    "sw_batch_download", "sw_stream", "sw_set_timing", "sw_kernel_times",
-    "sw_dist_unique_id", "sw_dist_init", "sw_dist_plan_solve", "sw_dist_shard_range",
-    "sw_dist_init_host", "sw_mmf_allocate", "sw_dist_plan_solve_dev", "sw_dist_enable_peer",
-    "sw_mmf_allocate_types", "sw_batch_keep_masks", "sw_ftf_allocate", "sw_ftf_allocate_batch",
-    "sw_wf_allocate", "sw_wf_allocate_batch", "sw_mtd_allocate", "sw_mtd_allocate_batch",
-    "sw_mst_allocate", "sw_mst_allocate_batch", "sw_allox_assign", "sw_allox_assign_batch",
-    "sw_wfh_allocate", "sw_wfh_allocate_batch", "sw_mmf_allocate_types_centred",
-    "sw_mmf_allocate_types_centred_batch", "sw_mtd_allocate_types", "sw_mtd_allocate_types_batch",
-    "sw_ftf_allocate_types", "sw_ftf_allocate_types_batch", "sw_wf_allocate_types", "sw_wf_allocate_types_batch",
-    "sw_mst_allocate_types", "sw_mst_allocate_types_batch",
-)
+# The per-job allocation policies of the allocation frame (csrc/sw_alloc.h):
+# the dtypes of the per-job columns in the order of the C arguments, their names
+# for the length error, and the number of levels per instance.
+_ALLOC = {
+    "ftf": ((np.int32, np.float64, np.float64, np.float64),
+            "scale_factors, full_time, elapsed and isolated_time", 2),
+    "wf": ((np.int32, np.float64), "scale_factors and coefficients", 2),
+    "mtd": ((np.int32, np.float64), "scale_factors and full_time", 2),
+    "mst": ((np.int32, np.float64, np.float64), "scale_factors, weights and floors", 4),
+}
+
+
+class _TypesPolicy(NamedTuple):
+    """A policy over worker types that differ (csrc/sw_types.h).  Its C
+    arguments are workers [n], scale factors [m], one [m, n] column, the [m]
+    columns, the allocation [m, n], the extra output and the result words."""
+    stem: str            # sw_<stem> and, with batch, sw_<stem>_batch
+    columns: tuple       # the names of the [m] columns
+    shapes: str          # the ValueError of an instance whose shapes do not fit
+    extra: str | None    # None, "levels" [m] or "prices" [n]
+    casts: tuple         # of the result words, one each: their number is the result's width
+    batch: bool = True
+
+
+_TYPES = {
+    "mmf": _TypesPolicy("mmf_allocate_types", (), "coefficients must be [num_jobs][num_types]", None,
+                        (float, int), batch=False),
+    "mmf_centred": _TypesPolicy("mmf_allocate_types_centred", (), "coefficients must be [num_jobs][num_types]", None,
+                                (float, int)),
+    "mtd": _TypesPolicy("mtd_allocate_types", ("steps",),
+                        "throughputs must be [num_jobs][num_types], steps [num_jobs]", None,
+                        (float, float, int, int)),
+    "ftf": _TypesPolicy("ftf_allocate_types", ("steps", "elapsed", "expected"),
+                        "throughputs must be [num_jobs][num_types], steps, elapsed and expected [num_jobs]", None,
+                        (float, float, int, int, int)),
+    "wf": _TypesPolicy("wf_allocate_types", (), "coefficients must be [num_jobs][num_types]", "levels",
+                       (float, int, int, int)),
+    "mst": _TypesPolicy("mst_allocate_types", (), "weights must be [num_jobs][num_types]", "prices",
+                        (float, int, int, int)),
+}
+
+# Every function include/shockwave_amd.h declares (checked by tests/test_abi.py)
+# → its argument types, or (argument types, restype) where that is not c_int.
+# load() declares them all.
+_h, _i32, _i64 = C.c_void_p, C.c_int32, C.c_int64
+_SIGNATURES = {
+    "sw_abi_version": [],
+    "sw_create": ([C.POINTER(SwConfig)], C.c_void_p),
+    "sw_destroy": ([_h], None),
+    "sw_last_error": ([_h], C.c_char_p),
+    "sw_create_error": ([], C.c_char_p),
+    "sw_plan_solve": [_h, C.POINTER(SwProblem), C.POINTER(SwResult)],
+    "sw_plan_solve_batch": [_h, _i32, C.POINTER(SwProblem), C.POINTER(SwResult)],
+    "sw_batch_upload": [_h, _i32, C.POINTER(SwProblem)],
+    "sw_batch_run": [_h],
+    "sw_batch_download": [_h, C.POINTER(SwResult)],
+    "sw_batch_keep_masks": [_h, _i32],
+    "sw_stream": ([_h], C.c_void_p),
+    "sw_set_timing": [_h, _i32],
+    "sw_kernel_times": [_h, _dp, _dp, _ip],
+    "sw_dist_unique_id": [C.c_void_p],
+    "sw_dist_init": [_h, C.c_void_p, _i32, _i32],
+    "sw_dist_plan_solve": [_h, C.POINTER(SwProblem), _i64, _i64, C.POINTER(SwResult)],
+    "sw_dist_plan_solve_dev": [_h, C.POINTER(SwProblem), _i64, _i64, C.POINTER(SwResult)],
+    "sw_dist_shard_range": [_i64, _i32, _i32, _lp, _lp],
+    "sw_dist_init_host": [_h, C.POINTER(SwHostComm), _i32, _i32],
+    "sw_dist_enable_peer": [_h, _i64],
+    "sw_mmf_allocate": [_h, _i32, _i32, _ip, _dp, _dp, _dp],
+    "sw_allox_assign": [_h, _i32, _i32, _ip, _dp, _dp, _ip, _ip, _ip, _dp],
+    "sw_allox_assign_batch": [_h, _i32, _lp, _ip, _ip, _dp, _dp, _ip, _ip, _ip, _lp, _dp],
+    "sw_wfh_allocate": [_h, _i32, _i32, _i32, _ip, _dp, _ip, _dp, _ip, _dp, _dp, _dp],
+    "sw_wfh_allocate_batch": [_h, _i32, _lp, _lp, _ip, _ip, _dp, _ip, _dp, _ip, _dp, _dp, _dp],
+}
+for _name, (_dtypes, _, _) in _ALLOC.items():
+    _cols = [_POINTER[np.dtype(t)] for t in _dtypes]
+    _SIGNATURES[f"sw_{_name}_allocate"] = [_h, _i32, _i32, *_cols, _dp, _dp]
+    _SIGNATURES[f"sw_{_name}_allocate_batch"] = [_h, _i32, _lp, _ip, *_cols, _dp, _dp]
+for _row in _TYPES.values():
+    _cols = [_ip, _ip, _dp, *[_dp] * len(_row.columns), _dp, *[_dp] * (_row.extra is not None), _dp]
+    _SIGNATURES["sw_" + _row.stem] = [_h, _i32, _i32, *_cols]
+    if _row.batch:
+        _SIGNATURES[f"sw_{_row.stem}_batch"] = [_h, _i32, _i32, _lp, *_cols]
+
+EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
 
 class NativeError(RuntimeError):
@@ -336,18 +409,6 @@ class NativeError(RuntimeError):
 
 
 _LIB = None
-
-
-# The per-job allocation policies of the allocation frame (csrc/sw_alloc.h):
-# the dtypes of the per-job columns in the order of the C arguments, their names
-# for the length error, and the number of levels per instance.
-_ALLOC = {
-    "ftf": ((np.int32, np.float64, np.float64, np.float64),
-            "scale_factors, full_time, elapsed and isolated_time", 2),
-    "wf": ((np.int32, np.float64), "scale_factors and coefficients", 2),
-    "mtd": ((np.int32, np.float64), "scale_factors and full_time", 2),
-    "mst": ((np.int32, np.float64, np.float64), "scale_factors, weights and floors", 4),
-}
 
 
 def load(path: str | None = None):
@@ -362,99 +423,41 @@ def load(path: str | None = None):
             f"{p} not found: build it with `python __graft_entry__.py build` "
             "(there is no CPU fallback for the plan solver)")
     lib = C.CDLL(p)
-    lib.sw_abi_version.restype = C.c_int
-    lib.sw_create.argtypes = [C.POINTER(SwConfig)]
-    lib.sw_create.restype = C.c_void_p
-    lib.sw_destroy.argtypes = [C.c_void_p]
-    lib.sw_destroy.restype = None
-    lib.sw_last_error.argtypes = [C.c_void_p]
-    lib.sw_last_error.restype = C.c_char_p
-    lib.sw_create_error.argtypes = []
-    lib.sw_create_error.restype = C.c_char_p
-    lib.sw_plan_solve.argtypes = [C.c_void_p, C.POINTER(SwProblem), C.POINTER(SwResult)]
-    lib.sw_plan_solve.restype = C.c_int
-    lib.sw_plan_solve_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(SwProblem),
-                                        C.POINTER(SwResult)]
-    lib.sw_plan_solve_batch.restype = C.c_int
-    lib.sw_batch_upload.argtypes = [C.c_void_p, C.c_int32, C.POINTER(SwProblem)]
-    lib.sw_batch_upload.restype = C.c_int
-    lib.sw_batch_run.argtypes = [C.c_void_p]
-    lib.sw_batch_run.restype = C.c_int
-    lib.sw_batch_download.argtypes = [C.c_void_p, C.POINTER(SwResult)]
-    lib.sw_batch_download.restype = C.c_int
-    lib.sw_batch_keep_masks.argtypes = [C.c_void_p, C.c_int32]
-    lib.sw_batch_keep_masks.restype = C.c_int
-    lib.sw_stream.argtypes = [C.c_void_p]
-    lib.sw_stream.restype = C.c_void_p
-    lib.sw_set_timing.argtypes = [C.c_void_p, C.c_int32]
-    lib.sw_set_timing.restype = C.c_int
-    lib.sw_kernel_times.argtypes = [C.c_void_p, _dp, _dp, _ip]
-    lib.sw_kernel_times.restype = C.c_int
-    lib.sw_dist_unique_id.argtypes = [C.c_void_p]
-    lib.sw_dist_unique_id.restype = C.c_int
-    lib.sw_dist_init.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
-    lib.sw_dist_init.restype = C.c_int
-    lib.sw_dist_plan_solve.argtypes = [C.c_void_p, C.POINTER(SwProblem), C.c_int64, C.c_int64,
-                                       C.POINTER(SwResult)]
-    lib.sw_dist_plan_solve.restype = C.c_int
-    lib.sw_dist_plan_solve_dev.argtypes = [C.c_void_p, C.POINTER(SwProblem), C.c_int64, C.c_int64,
-                                           C.POINTER(SwResult)]
-    lib.sw_dist_plan_solve_dev.restype = C.c_int
-    lib.sw_dist_shard_range.argtypes = [C.c_int64, C.c_int32, C.c_int32,
-                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    lib.sw_dist_shard_range.restype = C.c_int
-    lib.sw_dist_init_host.argtypes = [C.c_void_p, C.POINTER(SwHostComm), C.c_int32, C.c_int32]
-    lib.sw_dist_init_host.restype = C.c_int
-    lib.sw_dist_enable_peer.argtypes = [C.c_void_p, C.c_int64]
-    lib.sw_dist_enable_peer.restype = C.c_int
-    lib.sw_mmf_allocate.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip, _dp, _dp, _dp]
-    lib.sw_mmf_allocate.restype = C.c_int
-    lib.sw_mmf_allocate_types.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip, _ip, _dp, _dp, _dp]
-    lib.sw_mmf_allocate_types.restype = C.c_int
-    lib.sw_mmf_allocate_types_centred.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip, _ip, _dp, _dp, _dp]
-    lib.sw_mmf_allocate_types_centred.restype = C.c_int
-    lib.sw_mmf_allocate_types_centred_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), _ip,
-                                                        _ip, _dp, _dp, _dp]
-    lib.sw_mmf_allocate_types_centred_batch.restype = C.c_int
-    lib.sw_mtd_allocate_types.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip, _ip, _dp, _dp, _dp, _dp]
-    lib.sw_mtd_allocate_types.restype = C.c_int
-    lib.sw_mtd_allocate_types_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), _ip, _ip,
-                                                _dp, _dp, _dp, _dp]
-    lib.sw_mtd_allocate_types_batch.restype = C.c_int
-    lib.sw_ftf_allocate_types.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp]
-    lib.sw_ftf_allocate_types.restype = C.c_int
-    lib.sw_ftf_allocate_types_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), _ip, _ip,
-                                                _dp, _dp, _dp, _dp, _dp, _dp]
-    lib.sw_ftf_allocate_types_batch.restype = C.c_int
-    lib.sw_wf_allocate_types.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip, _ip, _dp, _dp, _dp, _dp]
-    lib.sw_wf_allocate_types.restype = C.c_int
-    lib.sw_wf_allocate_types_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), _ip, _ip,
-                                               _dp, _dp, _dp, _dp]
-    lib.sw_wf_allocate_types_batch.restype = C.c_int
-    lib.sw_mst_allocate_types.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip, _ip, _dp, _dp, _dp, _dp]
-    lib.sw_mst_allocate_types.restype = C.c_int
-    lib.sw_mst_allocate_types_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), _ip, _ip,
-                                                _dp, _dp, _dp, _dp]
-    lib.sw_mst_allocate_types_batch.restype = C.c_int
-    for name, (dtypes, _, _) in _ALLOC.items():
-        cols = [_ip if t is np.int32 else _dp for t in dtypes]
-        single, batch = getattr(lib, f"sw_{name}_allocate"), getattr(lib, f"sw_{name}_allocate_batch")
-        single.argtypes = [C.c_void_p, C.c_int32, C.c_int32, *cols, _dp, _dp]
-        batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _ip, *cols, _dp, _dp]
-        single.restype = batch.restype = C.c_int
-    lib.sw_allox_assign.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _ip, _dp, _dp, _ip, _ip, _ip, _dp]
-    lib.sw_allox_assign.restype = C.c_int
-    lib.sw_allox_assign_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _ip, _ip, _dp, _dp, _ip, _ip,
-                                          _ip, C.POINTER(C.c_int64), _dp]
-    lib.sw_allox_assign_batch.restype = C.c_int
-    lib.sw_wfh_allocate.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _ip, _dp, _ip, _dp, _ip, _dp, _dp, _dp]
-    lib.sw_wfh_allocate.restype = C.c_int
-    lib.sw_wfh_allocate_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _ip,
-                                          _ip, _dp, _ip, _dp, _ip, _dp, _dp, _dp]
-    lib.sw_wfh_allocate_batch.restype = C.c_int
+    for name, sig in _SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = sig if isinstance(sig, tuple) else (sig, C.c_int)
     if path is None:
         _LIB = lib
     return lib
+
+
+# The batch calls take their instances concatenated, in CSR form: instance i
+# owns [offsets[i], offsets[i + 1]) of every per-job array.
+def _offsets(lengths):
+    """The CSR offsets [count + 1] of instances of these lengths."""
+    off = np.zeros(len(lengths) + 1, dtype=np.int64)
+    off[1:] = np.cumsum(lengths)
+    return off
+
+
+def _column(parts, k, dtype):
+    """Column k of all parts, each flattened, concatenated as dtype: empty
+    when there are no parts; a part without the column (None) gives zeros as
+    long as its column 0."""
+    cols = [np.zeros(len(p[0]), dtype=dtype) if p[k] is None else p[k] for p in parts]
+    return np.ascontiguousarray(np.concatenate(cols, axis=None) if cols else [], dtype=dtype)
+
+
+def _split(v, off):
+    """Every instance's part of the output v, as copies."""
+    off = off.tolist()
+    return [v[a:b].copy() for a, b in zip(off[:-1], off[1:])]
+
+
+def _sent(built, override):
+    """The offsets C is given: the caller's override (tests only) where there
+    is one.  The outputs are sliced by the built ones either way."""
+    return built if override is None else np.ascontiguousarray(override, dtype=np.int64)
 
 
 class Solver:
@@ -511,7 +514,7 @@ class Solver:
                 ress[i].plan = None
             if masks:
                 m = np.zeros(a.N, dtype=np.uint64)
-                ress[i].plan_masks = m.ctypes.data_as(C.POINTER(C.c_uint64))
+                ress[i].plan_masks = _ptr(m)
                 mk.append(m)
         rc = self._check(self.lib.sw_plan_solve_batch(self.h, len(batch), probs, ress),
                          "sw_plan_solve_batch")
@@ -541,7 +544,7 @@ class Solver:
         if masks:
             for i, a in enumerate(self._batch):
                 m = np.zeros(max(a.N, 1), dtype=np.uint64)
-                ress[i].plan_masks = m.ctypes.data_as(C.POINTER(C.c_uint64))
+                ress[i].plan_masks = _ptr(m)
                 mk.append(m)
         rc = self._check(self.lib.sw_batch_download(self.h, ress), "sw_batch_download")
         out = [result_dict(ress[i], a, rc) for i, a in enumerate(self._batch)]
@@ -570,135 +573,100 @@ class Solver:
             raise ValueError("scale_factors and coefficients must have the same length")
         x = np.zeros(len(sf), dtype=np.float64)
         lvl = np.zeros(2, dtype=np.float64)
-        self._check(self.lib.sw_mmf_allocate(self.h, len(sf), int(num_workers),
-                                             sf.ctypes.data_as(_ip), c.ctypes.data_as(_dp),
-                                             x.ctypes.data_as(_dp), lvl.ctypes.data_as(_dp)),
+        self._check(self.lib.sw_mmf_allocate(self.h, len(sf), int(num_workers), *map(_ptr, (sf, c, x, lvl))),
                     "sw_mmf_allocate")
         return x, float(lvl[0]), float(lvl[1])
 
-    def mmf_allocate_types(self, workers, scale_factors, coefficients):
-        """x[j][k] of the heterogeneity-aware MaxMinFairness LP over worker
-        types (sw_mmf_allocate_types); returns (x [m, n], t*, pivots)."""
-        w = np.ascontiguousarray(workers, dtype=np.int32)
-        sf = np.ascontiguousarray(scale_factors, dtype=np.int32)
-        c = np.ascontiguousarray(coefficients, dtype=np.float64)
-        if c.ndim != 2 or c.shape != (len(sf), len(w)):
-            raise ValueError("coefficients must be [num_jobs][num_types]")
-        x = np.zeros(c.shape, dtype=np.float64)
-        lvl = np.zeros(2, dtype=np.float64)
-        self._check(self.lib.sw_mmf_allocate_types(self.h, c.shape[0], c.shape[1], w.ctypes.data_as(_ip),
-                                                   sf.ctypes.data_as(_ip), c.ctypes.data_as(_dp),
-                                                   x.ctypes.data_as(_dp), lvl.ctypes.data_as(_dp)),
-                    "sw_mmf_allocate_types")
-        return x, float(lvl[0]), int(lvl[1])
-
+    # ---- the policies over worker types that differ (csrc/sw_types.h; _TYPES above) ----
     @staticmethod
-    def _mmf_types_arrays(workers, scale_factors, coefficients):
+    def _types_arrays(row, workers, scale_factors, *columns):
+        """One instance's arguments as contiguous arrays of fitting shapes:
+        workers, scale factors, the [m, n] column, the row's [m] columns."""
+        if len(columns) != 1 + len(row.columns):
+            raise TypeError(f"sw_{row.stem} takes workers, scale factors and {1 + len(row.columns)} columns")
         w = np.ascontiguousarray(workers, dtype=np.int32)
         sf = np.ascontiguousarray(scale_factors, dtype=np.int32)
-        c = np.ascontiguousarray(coefficients, dtype=np.float64)
-        if c.ndim != 2 or c.shape != (len(sf), len(w)):
-            raise ValueError("coefficients must be [num_jobs][num_types]")
-        return w, sf, c
+        c, *cols = [np.ascontiguousarray(v, dtype=np.float64) for v in columns]
+        if c.ndim != 2 or c.shape != (len(sf), len(w)) or any([v.shape != (len(sf),) for v in cols]):
+            raise ValueError(row.shapes)
+        return [w, sf, c, *cols]
 
-    def _types_batch(self, what, arrays, ncols, instances, offsets, width, levels=False):
-        """sw_<what>_batch over a list of per-instance argument tuples with one
-        number of types (arrays: the policy's check of one instance, returning
-        ncols arrays: workers, scale factors, the [m, n] column, then the [m]
-        columns); returns per instance (x [m, n], levels [m] if the policy has
-        them, the width result words)."""
-        parts = [arrays(*inst) for inst in instances]
+    def _types(self, policy, *values):
+        """sw_<stem>; returns (x [m, n], the extra output if the policy has
+        one, the result words cast)."""
+        row = _TYPES[policy]
+        cols = self._types_arrays(row, *values)
+        m, n = cols[2].shape
+        x = np.zeros((m, n), dtype=np.float64)
+        extra = [np.zeros(m if row.extra == "levels" else n, dtype=np.float64)] if row.extra else []
+        res = np.zeros(len(row.casts), dtype=np.float64)
+        what = "sw_" + row.stem
+        self._check(getattr(self.lib, what)(self.h, m, n, *map(_ptr, (*cols, x, *extra, res))), what)
+        return (x, *extra, *[cast(v) for cast, v in zip(row.casts, res.tolist())])
+
+    def _types_batch(self, policy, instances, offsets):
+        """sw_<stem>_batch over a list of per-instance argument tuples with one
+        number of types; returns per instance what _types returns, the arrays
+        as copies."""
+        row = _TYPES[policy]
+        parts = [self._types_arrays(row, *inst) for inst in instances]
         count = len(parts)
         n = len(parts[0][0]) if parts else 1
         if any(len(p[0]) != n for p in parts):
             raise ValueError("every instance must have the same number of worker types")
-        off = np.zeros(count + 1, dtype=np.int64)
-        for i, p in enumerate(parts):
-            off[i + 1] = off[i] + len(p[1])
-        cat = [np.ascontiguousarray(np.concatenate([p[c].reshape(-1) for p in parts]) if parts else [],
-                                    dtype=np.int32 if c < 2 else np.float64) for c in range(ncols)]
+        off = _offsets([len(p[1]) for p in parts])
+        cat = [_column(parts, k, np.int32 if k < 2 else np.float64) for k in range(3 + len(row.columns))]
         x = np.zeros(len(cat[2]), dtype=np.float64)
-        lv = np.zeros(len(cat[1]), dtype=np.float64)
-        res = np.zeros((count, width), dtype=np.float64)
-        coff = off if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
-        outs = [x, lv, res] if levels else [x, res]
-        self._check(getattr(self.lib, what)(self.h, count, n, coff.ctypes.data_as(C.POINTER(C.c_int64)),
-                                            *map(self._ptr, cat + outs)), what)
-        return [(x[off[i] * n:off[i + 1] * n].reshape(-1, n).copy(),) +
-                ((lv[off[i]:off[i + 1]].copy(),) if levels else ()) + (res[i],) for i in range(count)]
+        # the extra output's own offsets: levels per job, prices per type
+        eoff = {None: None, "levels": off, "prices": n * np.arange(count + 1)}[row.extra]
+        extra = [] if eoff is None else [np.zeros(eoff[-1], dtype=np.float64)]
+        res = np.zeros((count, len(row.casts)), dtype=np.float64)
+        what = f"sw_{row.stem}_batch"
+        self._check(getattr(self.lib, what)(self.h, count, n, *map(_ptr, (_sent(off, offsets), *cat, x, *extra, res))),
+                    what)
+        words = [[cast(v) for v in word] for cast, word in zip(row.casts, res.T.tolist())]
+        return list(zip(_split(x.reshape(-1, n), off), *(_split(e, eoff) for e in extra), *words))
+
+    def mmf_allocate_types(self, workers, scale_factors, coefficients):
+        """x[j][k] of the heterogeneity-aware MaxMinFairness LP over worker
+        types (sw_mmf_allocate_types); returns (x [m, n], t*, pivots)."""
+        return self._types("mmf", workers, scale_factors, coefficients)
 
     def mmf_allocate_types_centred(self, workers, scale_factors, coefficients):
         """The LP of mmf_allocate_types with the analytic centre of its optimal
         face as the allocation, the point ECOS converges to
         (sw_mmf_allocate_types_centred); returns (x [m, n], t*, Newton steps)."""
-        w, sf, c = self._mmf_types_arrays(workers, scale_factors, coefficients)
-        x = np.zeros(c.shape, dtype=np.float64)
-        lvl = np.zeros(2, dtype=np.float64)
-        self._check(self.lib.sw_mmf_allocate_types_centred(self.h, c.shape[0], c.shape[1], w.ctypes.data_as(_ip),
-                                                           sf.ctypes.data_as(_ip), c.ctypes.data_as(_dp),
-                                                           x.ctypes.data_as(_dp), lvl.ctypes.data_as(_dp)),
-                    "sw_mmf_allocate_types_centred")
-        return x, float(lvl[0]), int(lvl[1])
+        return self._types("mmf_centred", workers, scale_factors, coefficients)
 
     def mmf_allocate_types_centred_batch(self, instances, offsets=None):
         """sw_mmf_allocate_types_centred_batch over a list of (workers,
         scale_factors, coefficients) tuples with one number of types, one kernel
         launch; returns the list of (x [m, n], t*, Newton steps).  offsets
         (tests only) overrides the CSR offsets built from the instances."""
-        return [(x, float(r[0]), int(r[1])) for x, r in self._types_batch(
-            "sw_mmf_allocate_types_centred_batch", self._mmf_types_arrays, 3, instances, offsets, 2)]
+        return self._types_batch("mmf_centred", instances, offsets)
 
     # ---- MinTotalDuration over worker types that differ (csrc/sw_mtd_types.h) ----
     MTDT_IDLE = 1  # flags of mtd_allocate_types: no job has steps left
     MTDT_THIN = 2  # the polytope at T is too thin to centre in (sw_mtd_types.h)
-
-    @staticmethod
-    def _mtd_types_arrays(workers, scale_factors, throughputs, steps):
-        w = np.ascontiguousarray(workers, dtype=np.int32)
-        sf = np.ascontiguousarray(scale_factors, dtype=np.int32)
-        thr = np.ascontiguousarray(throughputs, dtype=np.float64)
-        st = np.ascontiguousarray(steps, dtype=np.float64)
-        if thr.ndim != 2 or thr.shape != (len(sf), len(w)) or st.shape != (len(sf),):
-            raise ValueError("throughputs must be [num_jobs][num_types], steps [num_jobs]")
-        return w, sf, thr, st
 
     def mtd_allocate_types(self, workers, scale_factors, throughputs, steps):
         """The MinTotalDuration allocation over worker types whose throughputs
         differ (sw_mtd_allocate_types): the reference's search over T on the
         max-min level t* of throughput / steps, and the analytic centre of its
         LP at the found T; returns (x [m, n], T, t*, Newton steps, flags)."""
-        w, sf, thr, st = self._mtd_types_arrays(workers, scale_factors, throughputs, steps)
-        x = np.zeros(thr.shape, dtype=np.float64)
-        res = np.zeros(4, dtype=np.float64)
-        self._check(self.lib.sw_mtd_allocate_types(self.h, thr.shape[0], thr.shape[1], w.ctypes.data_as(_ip),
-                                                   sf.ctypes.data_as(_ip), thr.ctypes.data_as(_dp),
-                                                   st.ctypes.data_as(_dp), x.ctypes.data_as(_dp),
-                                                   res.ctypes.data_as(_dp)),
-                    "sw_mtd_allocate_types")
-        return x, float(res[0]), float(res[1]), int(res[2]), int(res[3])
+        return self._types("mtd", workers, scale_factors, throughputs, steps)
 
     def mtd_allocate_types_batch(self, instances, offsets=None):
         """sw_mtd_allocate_types_batch over a list of (workers, scale_factors,
         throughputs, steps) tuples with one number of types, one kernel launch;
         returns the list of (x [m, n], T, t*, Newton steps, flags).  offsets
         (tests only) overrides the CSR offsets built from the instances."""
-        return [(x, float(r[0]), float(r[1]), int(r[2]), int(r[3])) for x, r in self._types_batch(
-            "sw_mtd_allocate_types_batch", self._mtd_types_arrays, 4, instances, offsets, 4)]
+        return self._types_batch("mtd", instances, offsets)
 
     # ---- FinishTimeFairness over worker types that differ (csrc/sw_ftf_types.h) ----
     FTFT_BOX = 1   # flags of ftf_allocate_types: ρ* is the least level the time rows admit
     FTFT_IDLE = 2  # no job has steps left
     FTFT_SAFE = 4  # a Newton step on t* overshot, steps on 1/t* from then on
-
-    @staticmethod
-    def _ftf_types_arrays(workers, scale_factors, throughputs, steps, elapsed, expected):
-        w = np.ascontiguousarray(workers, dtype=np.int32)
-        sf = np.ascontiguousarray(scale_factors, dtype=np.int32)
-        thr = np.ascontiguousarray(throughputs, dtype=np.float64)
-        cols = [np.ascontiguousarray(v, dtype=np.float64) for v in (steps, elapsed, expected)]
-        if thr.ndim != 2 or thr.shape != (len(sf), len(w)) or any(c.shape != (len(sf),) for c in cols):
-            raise ValueError("throughputs must be [num_jobs][num_types], steps, elapsed and expected [num_jobs]")
-        return (w, sf, thr) + tuple(cols)
 
     def ftf_allocate_types(self, workers, scale_factors, throughputs, steps, elapsed, expected):
         """The FinishTimeFairness allocation over worker types whose throughputs
@@ -706,16 +674,7 @@ class Solver:
         level of throughput·(ρ·expected − elapsed)/steps, and the analytic centre
         of the program's feasible set at ρ*; returns (x [m, n], ρ*, t*(ρ*),
         Newton steps, level solves, flags)."""
-        w, sf, thr, st, el, ex = self._ftf_types_arrays(workers, scale_factors, throughputs, steps, elapsed, expected)
-        x = np.zeros(thr.shape, dtype=np.float64)
-        res = np.zeros(5, dtype=np.float64)
-        self._check(self.lib.sw_ftf_allocate_types(self.h, thr.shape[0], thr.shape[1], w.ctypes.data_as(_ip),
-                                                   sf.ctypes.data_as(_ip), thr.ctypes.data_as(_dp),
-                                                   st.ctypes.data_as(_dp), el.ctypes.data_as(_dp),
-                                                   ex.ctypes.data_as(_dp), x.ctypes.data_as(_dp),
-                                                   res.ctypes.data_as(_dp)),
-                    "sw_ftf_allocate_types")
-        return x, float(res[0]), float(res[1]), int(res[2]), int(res[3]), int(res[4])
+        return self._types("ftf", workers, scale_factors, throughputs, steps, elapsed, expected)
 
     def ftf_allocate_types_batch(self, instances, offsets=None):
         """sw_ftf_allocate_types_batch over a list of (workers, scale_factors,
@@ -723,8 +682,7 @@ class Solver:
         one kernel launch; returns the list of (x [m, n], ρ*, t*(ρ*), Newton
         steps, level solves, flags).  offsets (tests only) overrides the CSR
         offsets built from the instances."""
-        return [(x, float(r[0]), float(r[1]), int(r[2]), int(r[3]), int(r[4])) for x, r in self._types_batch(
-            "sw_ftf_allocate_types_batch", self._ftf_types_arrays, 6, instances, offsets, 5)]
+        return self._types_batch("ftf", instances, offsets)
 
     WFT_ONE = 1   # flags of wf_allocate_types: a single stage froze every job
     WFT_NEAR = 2  # a job's statistic came within a factor 10 of the bottleneck threshold
@@ -736,16 +694,7 @@ class Solver:
         vector of Σ_k coefficients·x by stages and the analytic centre of the
         last stage's optimal face; returns (x [m, n], levels [m], last level,
         Newton steps, stages, flags)."""
-        w, sf, c = self._mmf_types_arrays(workers, scale_factors, coefficients)
-        x = np.zeros(c.shape, dtype=np.float64)
-        lv = np.zeros(c.shape[0], dtype=np.float64)
-        res = np.zeros(4, dtype=np.float64)
-        self._check(self.lib.sw_wf_allocate_types(self.h, c.shape[0], c.shape[1], w.ctypes.data_as(_ip),
-                                                  sf.ctypes.data_as(_ip), c.ctypes.data_as(_dp),
-                                                  x.ctypes.data_as(_dp), lv.ctypes.data_as(_dp),
-                                                  res.ctypes.data_as(_dp)),
-                    "sw_wf_allocate_types")
-        return x, lv, float(res[0]), int(res[1]), int(res[2]), int(res[3])
+        return self._types("wf", workers, scale_factors, coefficients)
 
     def wf_allocate_types_batch(self, instances, offsets=None):
         """sw_wf_allocate_types_batch over a list of (workers, scale_factors,
@@ -753,8 +702,7 @@ class Solver:
         returns the list of (x [m, n], levels [m], last level, Newton steps,
         stages, flags).  offsets (tests only) overrides the CSR offsets built
         from the instances."""
-        return [(x, lv, float(r[0]), int(r[1]), int(r[2]), int(r[3])) for x, lv, r in self._types_batch(
-            "sw_wf_allocate_types_batch", self._mmf_types_arrays, 3, instances, offsets, 4, levels=True)]
+        return self._types_batch("wf", instances, offsets)
 
     # ---- the per-job allocation policies (csrc/sw_alloc.h; _ALLOC above) ----
     @staticmethod
@@ -767,18 +715,13 @@ class Solver:
             raise ValueError(f"{names} must have the same length")
         return cols
 
-    @staticmethod
-    def _ptr(a):
-        return None if a is None else a.ctypes.data_as(_ip if a.dtype == np.int32 else _dp)
-
     def _alloc(self, policy, values, num_workers):
         """sw_<policy>_allocate; returns (x, levels)."""
         cols = self._alloc_columns(policy, values)
         x = np.zeros(len(cols[0]), dtype=np.float64)
         lvl = np.zeros(_ALLOC[policy][2], dtype=np.float64)
         what = f"sw_{policy}_allocate"
-        self._check(getattr(self.lib, what)(self.h, len(cols[0]), int(num_workers), *map(self._ptr, cols),
-                                            self._ptr(x), self._ptr(lvl)), what)
+        self._check(getattr(self.lib, what)(self.h, len(cols[0]), int(num_workers), *map(_ptr, (*cols, x, lvl))), what)
         return x, lvl
 
     def _alloc_batch(self, policy, instances, offsets):
@@ -788,21 +731,15 @@ class Solver:
         dtypes, _, width = _ALLOC[policy]
         parts = [self._alloc_columns(policy, inst[:len(dtypes)]) for inst in instances]
         count = len(parts)
-        off = np.zeros(count + 1, dtype=np.int64)
-        for i, q in enumerate(parts):
-            off[i + 1] = off[i] + len(q[0])
-        cat = [None if parts and all(q[k] is None for q in parts) else
-               np.ascontiguousarray(np.concatenate([np.zeros(len(q[0]), dtype=t) if q[k] is None else q[k]
-                                                    for q in parts]) if parts else [], dtype=t)
+        off = _offsets([len(q[0]) for q in parts])
+        cat = [None if parts and all(q[k] is None for q in parts) else _column(parts, k, t)
                for k, t in enumerate(dtypes)]
         g = np.ascontiguousarray([int(inst[len(dtypes)]) for inst in instances], dtype=np.int32)
         x = np.zeros(len(cat[0]), dtype=np.float64)
         lvl = np.zeros((count, width), dtype=np.float64)
-        coff = off if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
         what = f"sw_{policy}_allocate_batch"
-        self._check(getattr(self.lib, what)(self.h, count, coff.ctypes.data_as(C.POINTER(C.c_int64)), self._ptr(g),
-                                            *map(self._ptr, cat), self._ptr(x), self._ptr(lvl)), what)
-        return [(x[off[i]:off[i + 1]].copy(), lvl[i]) for i in range(count)]
+        self._check(getattr(self.lib, what)(self.h, count, *map(_ptr, (_sent(off, offsets), g, *cat, x, lvl))), what)
+        return list(zip(_split(x, off), lvl))
 
     # ---- Gavel FinishTimeFairness allocation (include/shockwave_amd.h sw_ftf_allocate) ----
     def ftf_allocate(self, scale_factors, full_time, elapsed, isolated_time, num_workers: int):
@@ -855,7 +792,7 @@ class Solver:
         g = np.zeros(len(w), dtype=np.float64)
         lvl = np.zeros(2, dtype=np.float64)
         self._check(self.lib.sw_wfh_allocate(self.h, len(sf), len(w), int(num_workers),
-                                             *map(self._ptr, (sf, c, ent, w, modes, x, g, lvl))), "sw_wfh_allocate")
+                                             *map(_ptr, (sf, c, ent, w, modes, x, g, lvl))), "sw_wfh_allocate")
         return x, g, float(lvl[0]), float(lvl[1])
 
     def wfh_allocate_batch(self, instances, job_offsets=None, entity_offsets=None):
@@ -866,23 +803,16 @@ class Solver:
         instances' lengths."""
         parts = [self._wfh_arrays(*inst[:5]) for inst in instances]
         count = len(parts)
-        off, eoff = np.zeros(count + 1, dtype=np.int64), np.zeros(count + 1, dtype=np.int64)
-        for i, q in enumerate(parts):
-            off[i + 1], eoff[i + 1] = off[i] + len(q[0]), eoff[i] + len(q[3])
-        dtypes = (np.int32, np.float64, np.int32, np.float64, np.int32)
-        cat = [np.ascontiguousarray(np.concatenate([q[k] for q in parts]) if parts else [], dtype=t)
-               for k, t in enumerate(dtypes)]
+        off, eoff = _offsets([len(q[0]) for q in parts]), _offsets([len(q[3]) for q in parts])
+        cat = [_column(parts, k, t) for k, t in enumerate((np.int32, np.float64, np.int32, np.float64, np.int32))]
         gw = np.ascontiguousarray([int(inst[5]) for inst in instances], dtype=np.int32)
         x = np.zeros(len(cat[0]), dtype=np.float64)
         g = np.zeros(len(cat[3]), dtype=np.float64)
         lvl = np.zeros((count, 2), dtype=np.float64)
-        coff = off if job_offsets is None else np.ascontiguousarray(job_offsets, dtype=np.int64)
-        ceoff = eoff if entity_offsets is None else np.ascontiguousarray(entity_offsets, dtype=np.int64)
-        lp = C.POINTER(C.c_int64)
-        self._check(self.lib.sw_wfh_allocate_batch(self.h, count, coff.ctypes.data_as(lp), ceoff.ctypes.data_as(lp),
-                                                   *map(self._ptr, (gw, *cat, x, g, lvl))), "sw_wfh_allocate_batch")
-        return [(x[off[i]:off[i + 1]].copy(), g[eoff[i]:eoff[i + 1]].copy(), float(lvl[i, 0]), float(lvl[i, 1]))
-                for i in range(count)]
+        self._check(self.lib.sw_wfh_allocate_batch(
+            self.h, count, *map(_ptr, (_sent(off, job_offsets), _sent(eoff, entity_offsets), gw, *cat, x, g, lvl))),
+            "sw_wfh_allocate_batch")
+        return list(zip(_split(x, off), _split(g, eoff), *lvl.T.tolist()))
 
     # ---- Gavel MinTotalDuration allocation (include/shockwave_amd.h sw_mtd_allocate) ----
     def mtd_allocate(self, scale_factors, full_time, num_workers: int):
@@ -917,28 +847,12 @@ class Solver:
     MSTT_UNPLACED = 1  # flags of mst_allocate_types: some unit stayed unallocated
     MSTT_SLACK = 2     # no type with workers is saturated
 
-    @staticmethod
-    def _mst_types_arrays(workers, scale_factors, weights):
-        w = np.ascontiguousarray(workers, dtype=np.int32)
-        sf = np.ascontiguousarray(scale_factors, dtype=np.int32)
-        wt = np.ascontiguousarray(weights, dtype=np.float64)
-        if wt.ndim != 2 or wt.shape != (len(sf), len(w)):
-            raise ValueError("weights must be [num_jobs][num_types]")
-        return w, sf, wt
-
     def mst_allocate_types(self, workers, scale_factors, weights):
         """The max-sum-throughput allocation over worker types whose weights
         (throughput / cost) differ (sw_mst_allocate_types): the exact vertex of
         the transportation problem by successive best paths; returns (x [m, n],
         prices [n], objective, augmentations, row recomputations, flags)."""
-        w, sf, wt = self._mst_types_arrays(workers, scale_factors, weights)
-        x = np.zeros(wt.shape, dtype=np.float64)
-        prices = np.zeros(len(w), dtype=np.float64)
-        res = np.zeros(4, dtype=np.float64)
-        self._check(self.lib.sw_mst_allocate_types(self.h, wt.shape[0], wt.shape[1],
-                                                   *map(self._ptr, (w, sf, wt, x, prices, res))),
-                    "sw_mst_allocate_types")
-        return x, prices, float(res[0]), int(res[1]), int(res[2]), int(res[3])
+        return self._types("mst", workers, scale_factors, weights)
 
     def mst_allocate_types_batch(self, instances, offsets=None):
         """sw_mst_allocate_types_batch over a list of (workers, scale_factors,
@@ -946,25 +860,7 @@ class Solver:
         list of (x [m, n], prices [n], objective, augmentations, row
         recomputations, flags).  offsets (tests only) overrides the CSR offsets
         built from the instances."""
-        parts = [self._mst_types_arrays(*inst) for inst in instances]
-        count = len(parts)
-        n = len(parts[0][0]) if parts else 1
-        if any(len(p[0]) != n for p in parts):
-            raise ValueError("every instance must have the same number of worker types")
-        off = np.zeros(count + 1, dtype=np.int64)
-        for i, p in enumerate(parts):
-            off[i + 1] = off[i] + len(p[1])
-        cat = [np.ascontiguousarray(np.concatenate([p[c].reshape(-1) for p in parts]) if parts else [],
-                                    dtype=np.int32 if c < 2 else np.float64) for c in range(3)]
-        x = np.zeros(len(cat[2]), dtype=np.float64)
-        prices = np.zeros((count, n), dtype=np.float64)
-        res = np.zeros((count, 4), dtype=np.float64)
-        coff = off if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
-        self._check(self.lib.sw_mst_allocate_types_batch(self.h, count, n, coff.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                         *map(self._ptr, cat + [x, prices, res])),
-                    "sw_mst_allocate_types_batch")
-        return [(x[off[i] * n:off[i + 1] * n].reshape(-1, n).copy(), prices[i].copy(), float(res[i, 0]),
-                 int(res[i, 1]), int(res[i, 2]), int(res[i, 3])) for i in range(count)]
+        return self._types_batch("mst", instances, offsets)
 
     # ---- AlloX assignment (include/shockwave_amd.h sw_allox_assign) ----
     @staticmethod
@@ -986,10 +882,8 @@ class Solver:
         jp = np.zeros(m, dtype=np.int32)
         wf = np.full(max(n, 1), -1, dtype=np.int32)
         cost = C.c_double(0.0)
-        self._check(self.lib.sw_allox_assign(self.h, m, len(free), free.ctypes.data_as(_ip), p.ctypes.data_as(_dp),
-                                             d.ctypes.data_as(_dp), jw.ctypes.data_as(_ip), jp.ctypes.data_as(_ip),
-                                             wf.ctypes.data_as(_ip), C.byref(cost)),
-                    "sw_allox_assign")
+        self._check(self.lib.sw_allox_assign(self.h, m, len(free), *map(_ptr, (free, p, d, jw, jp, wf)),
+                                             C.byref(cost)), "sw_allox_assign")
         return jw, jp, wf[:n].copy(), float(cost.value)
 
     def allox_assign_batch(self, instances):
@@ -998,32 +892,22 @@ class Solver:
         job_position, worker_first, cost)."""
         parts = [self._allox_arrays(*inst) for inst in instances]
         count = len(parts)
-        joff = np.zeros(count + 1, dtype=np.int64)
-        woff = np.zeros(count + 1, dtype=np.int64)
+        if any(len(f) > 8 for f, _, _ in parts):
+            raise ValueError("at most 8 worker types")
+        joff = _offsets([len(d) for _, _, d in parts])
+        woff = _offsets([int(np.clip(f, 0, None).sum()) for f, _, _ in parts])
         free = np.zeros((count, 8), dtype=np.int32)
-        nt = np.zeros(count, dtype=np.int32)
-        for i, (f, p, d) in enumerate(parts):
-            if len(f) > 8:
-                raise ValueError("at most 8 worker types")
-            joff[i + 1] = joff[i] + len(d)
-            woff[i + 1] = woff[i] + int(np.clip(f, 0, None).sum())
+        for i, (f, _, _) in enumerate(parts):
             free[i, :len(f)] = f
-            nt[i] = len(f)
-        p = np.ascontiguousarray(np.concatenate([q[1].reshape(-1) for q in parts]) if parts else [], dtype=np.float64)
-        d = np.ascontiguousarray(np.concatenate([q[2] for q in parts]) if parts else [], dtype=np.float64)
+        nt = np.ascontiguousarray([len(f) for f, _, _ in parts], dtype=np.int32)
+        p, d = _column(parts, 1, np.float64), _column(parts, 2, np.float64)
         jw = np.full(len(d), -1, dtype=np.int32)
         jp = np.zeros(len(d), dtype=np.int32)
         wf = np.full(max(int(woff[-1]), 1), -1, dtype=np.int32)
         costs = np.zeros(max(count, 1), dtype=np.float64)
-        lp = C.POINTER(C.c_int64)
-        self._check(self.lib.sw_allox_assign_batch(self.h, count, joff.ctypes.data_as(lp), nt.ctypes.data_as(_ip),
-                                                   free.ctypes.data_as(_ip), p.ctypes.data_as(_dp),
-                                                   d.ctypes.data_as(_dp), jw.ctypes.data_as(_ip),
-                                                   jp.ctypes.data_as(_ip), wf.ctypes.data_as(_ip),
-                                                   woff.ctypes.data_as(lp), costs.ctypes.data_as(_dp)),
-                    "sw_allox_assign_batch")
-        return [(jw[joff[i]:joff[i + 1]].copy(), jp[joff[i]:joff[i + 1]].copy(), wf[woff[i]:woff[i + 1]].copy(),
-                 float(costs[i])) for i in range(count)]
+        self._check(self.lib.sw_allox_assign_batch(self.h, count, *map(_ptr, (joff, nt, free, p, d, jw, jp, wf, woff,
+                                                                              costs))), "sw_allox_assign_batch")
+        return list(zip(_split(jw, joff), _split(jp, joff), _split(wf, woff), costs[:count].tolist()))
 
     # ---- sharded single instance (include/shockwave_amd.h sw_dist_*) ----
     def dist_init(self, unique_id: bytes, rank: int, world: int):
