@@ -122,8 +122,10 @@ typedef struct sw_problem {
  * bit t = plan[j][t] — 8 bytes per job across the host boundary instead of
  * future_rounds.  Any of plan / plan_masks / planned_rounds may be NULL; the
  * batch entry points copy back only what some result of the batch asks for.
- * The sharded entry points (sw_dist_*) write plan and planned_rounds only and
- * reject a non-NULL plan_masks.
+ * The sharded entry points (sw_dist_plan_solve, sw_dist_plan_solve_dev) take
+ * the same three, each rank for its own jobs: plan_masks[i] is local job i's
+ * word, bits at and above future_rounds 0; a rank copies back future_rounds
+ * bytes per job only when plan is set, 8 when plan_masks is.
  */
 typedef struct sw_result {
     uint8_t* plan;
@@ -279,8 +281,10 @@ int sw_dist_shard_range(int64_t total_jobs, int32_t world, int32_t rank, int64_t
 /*
  * Device-resident variant ("host (or device) pointers"):
  * local's per-job arrays are device pointers on the handle's device, and
- * res->plan / res->planned_rounds are device pointers (or NULL), written on
- * the handle's stream — nothing crosses PCIe but the step scalars.  The
+ * res->plan / res->plan_masks / res->planned_rounds are device pointers on
+ * that device (each may be NULL; plan at any alignment, plan_masks 8-byte
+ * aligned), written on the handle's stream — nothing crosses PCIe but the
+ * step scalars.  The
  * per-job checks of the host path run on the device; a bad input on any rank
  * returns SW_ERR_INVALID on every rank.  Synchronous like sw_dist_plan_solve.
  */

@@ -15,7 +15,8 @@
  *
  * Layout in HBM (per rank, NL local jobs, T rounds):
  *   jc[NL] (sw_jobc, 64 B)   keys[NL][T] fp32   l, taken, 5 count arrays [NL] i32
- *   3 round-bitmask arrays [NL] u64   plan[NL][T] u8   planned[NL] i32
+ *   3 round-bitmask arrays [NL] u64   planned[NL] i32
+ *   plan[NL][T] u8 / masks[NL] u64: the outputs a result asks for, only
  *   red[128] i64 (step results)   exchange blocks for the gathers
  *   placement: send[P] / all[W·P] entries (24 B), chunk-sorted keys and
  *   entries [W·P rounded up to 1024], order[W·P]
@@ -33,6 +34,9 @@
  *        deterministic-sum lane sums its jobs left to right (sw_detsum's
  *        chunks), so the gathered lanes reproduce the single-instance sums
  *        bit for bit; one launch per reduction step
+ *   k_emit_plan   the final masks as the caller's plan: the words, and / or
+ *        T bytes per job — a wave per 64 jobs writes their contiguous bytes
+ *        as 16-byte chunks built from the masks in LDS
  *   k_pack_chunk_sort / k_pack_merge_rank   the global placement order: LDS
  *        bitonic sort per 1024-entry chunk, ranks by binary searches in the
  *        other sorted chunks
@@ -118,7 +122,8 @@ struct ShardDev {
     double* xa;   /* per-job values of the last reduction (two rows of NL) */
     int32_t* arr[SW_A_COUNT];
     uint64_t* y[SW_Y_COUNT];
-    uint8_t* plan;
+    uint8_t* plan;   /* nullptr: no result wants the bytes */
+    uint64_t* masks; /* nullptr: no result wants the words  */
     int32_t* planned;
     long long* red; /* i64 / u64-bit step results */
     /* fused publish (world 1): the kernel's last block stores the step result
@@ -978,8 +983,8 @@ __global__ void k_fill_apply(ShardDev S, int i, int t) {
  * to right — so the gathered lanes reproduce the single-instance sums bit for
  * bit.  max g and the integer sum go to red[0] / red[1] by atomics; the last
  * block to finish (counter red[kRedCtr]) copies them behind the lanes.
- * out = [A lanes][B lanes][gm][isum].  SW_EV_FINAL also writes the plan row
- * and count of each job. */
+ * out = [A lanes][B lanes][gm][isum].  SW_EV_FINAL also writes the count of
+ * each job (its plan: k_emit_plan, behind the step). */
 /* sel = kEvSelUmax (fast_solve): SW_EV_SELECT's A, B, max g and a third
  * lane sum C = f(T_j) (SW_EV_UMAX's A) in one pass, out = [A][B][gm][isum][C] */
 constexpr int kEvSelUmax = 7;
@@ -1019,13 +1024,8 @@ __global__ __launch_bounds__(kTB) void k_eval(ShardDev S, int sel, const int32_t
         } else { /* SW_EV_FINAL */
             const uint64_t m = ysrc[i];
             const int cn = __popcll(m);
-            long long Ssum = 0;
-            uint8_t* row = S.plan + (size_t)i * S.T;
-            for (int t = 0; t < S.T; ++t) {
-                const uint32_t bit = (uint32_t)((m >> t) & 1ull);
-                Ssum += bit ? t : 0;
-                row[t] = (uint8_t)bit;
-            }
+            long long Ssum = 0; /* the plan itself: k_emit_plan */
+            for (int t = 0; t < S.T; ++t) Ssum += ((m >> t) & 1ull) ? t : 0;
             S.planned[i] = cn;
             fa = sw_f(&c, cn, S.nb, S.beta, S.ell, S.slope);
             fb = cn > 0 ? ((double)Ssum / (double)cn) * S.p[i] : 0.0;
@@ -1081,6 +1081,74 @@ __global__ __launch_bounds__(kTB) void k_eval(ShardDev S, int sel, const int32_t
         __threadfence();
         __syncthreads();
         pub_store(S);
+    }
+}
+
+/* ---- the plan, out of the final step's round masks ----------------------------
+ * k_emit_plan behind SW_EV_FINAL, in the layouts the caller's result asked for
+ * (include/shockwave_amd.h sw_result): S.masks — the words themselves, one
+ * coalesced store per lane — and S.plan, T bytes per job.  One wave owns 64
+ * consecutive jobs, so its 64·T plan bytes are one contiguous run of HBM: the
+ * wave stages its 64 masks in LDS and its lanes write the run as 16-byte
+ * chunks on the 16-byte grid of the address (S.plan may be a caller's tensor
+ * at any alignment, and T is arbitrary), each chunk built from the masks of
+ * the ≤ 16 jobs it crosses.  Only the run's two ragged ends are byte stores.
+ * (A thread per job storing its own row would touch 64 lines per store
+ * instruction.) */
+
+/* eight plan bytes from the low eight bits of x: byte b = bit b */
+__device__ __forceinline__ uint64_t spread8(uint64_t x) {
+    const uint64_t sel = ((x & 0xFFull) * 0x0101010101010101ull) & 0x8040201008040201ull; /* byte b: bit b or 0 */
+    return ((sel + 0x7F7F7F7F7F7F7F7Full) >> 7) & 0x0101010101010101ull;
+}
+
+/* the eight plan bytes from (job j, round t) on, (j, t) advanced past them;
+ * ms[64] = 0 ends the walk behind the wave's last job */
+__device__ __forceinline__ uint64_t plan_bytes8(const uint64_t* ms, int T, int& j, int& t) {
+    uint64_t r;
+    if (T - t >= 8) { /* inside one row */
+        r = spread8(ms[j] >> t);
+        t += 8;
+    } else {
+        r = 0;
+        for (int b = 0; b < 8; ++b) {
+            r |= ((ms[j] >> t) & 1ull) << (8 * b);
+            if (++t == T) { t = 0; ++j; }
+        }
+    }
+    if (t == T) { t = 0; ++j; }
+    return r;
+}
+
+constexpr int kEmitJobs = 64; /* jobs of one wave of k_emit_plan */
+__global__ __launch_bounds__(kTB) void k_emit_plan(ShardDev S, const uint64_t* ysrc) {
+    __shared__ uint64_t msh[kTB / 64][kEmitJobs + 1];
+    const int lane = lane_id();
+    uint64_t* ms = msh[wave_id()];
+    const int64_t j0 = ((int64_t)blockIdx.x * (kTB / 64) + wave_id()) * kEmitJobs;
+    const int nj = (int)max((int64_t)0, min((int64_t)kEmitJobs, (int64_t)S.NL - j0)); /* 0: a wave past the end */
+    const uint64_t m = lane < nj ? ysrc[j0 + lane] : 0;
+    if (S.masks && lane < nj) S.masks[j0 + lane] = m;
+    if (!S.plan) return;
+    ms[lane] = m;
+    if (lane == 0) ms[kEmitJobs] = 0;
+    __syncthreads();
+    const int T = S.T, nb = nj * T; /* the run: bytes [0, nb) from g */
+    uint8_t* g = S.plan + (size_t)j0 * T;
+    const int mis = (int)(reinterpret_cast<uintptr_t>(g) & 15); /* chunk c: bytes [16c − mis, 16c − mis + 16) */
+    for (int c = lane; 16 * c - mis < nb; c += 64) {
+        const int lo = 16 * c - mis;
+        if (lo >= 0 && lo + 16 <= nb) {
+            int j = lo / T, t = lo - j * T;
+            const uint64_t a = plan_bytes8(ms, T, j, t), b = plan_bytes8(ms, T, j, t);
+            *reinterpret_cast<uint4*>(g + lo) =
+                make_uint4((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32));
+        } else { /* a ragged end: the neighbouring run (or nothing) owns the rest of the chunk */
+            for (int o = max(lo, 0); o < min(lo + 16, nb); ++o) {
+                const int j = o / T;
+                g[o] = (uint8_t)((ms[j] >> (o - j * T)) & 1ull);
+            }
+        }
     }
 }
 
@@ -2454,7 +2522,7 @@ struct sw_shard_state {
     DevBuf<double> d, R, p, xrecv; /* gathers run in place: rank r's block is its send buffer */
     DevBuf<sw_jobc> jc;
     DevBuf<float> keys;
-    DevBuf<uint64_t> y[SW_Y_COUNT];
+    DevBuf<uint64_t> y[SW_Y_COUNT], masks;
     DevBuf<uint8_t> plan;
     DevBuf<long long> red, tieblk;
     DevBuf<sw_pack_ent> pall;
@@ -3059,6 +3127,15 @@ int eval_enqueue(sw_shard_state* S, int32_t sel, int32_t arg, const double** vie
     return SW_OK;
 }
 
+/* The plan of the final step's masks Y[ysel], behind that step on the stream
+ * and off its path to the host: nothing the step reduces depends on it. */
+int emit_enqueue(sw_shard_state* S, int32_t ysel) {
+    if (S->NL && (S->dv.plan || S->dv.masks))
+        LAUNCH(S, k_emit_plan, dim3(nblk(S->NL)), dim3(kTB), 0, S->h->stream, S->dv,
+               (const uint64_t*)S->y[ysel].p);
+    return SW_OK;
+}
+
 int op_eval(void* ctx, int32_t sel, int32_t arg, double* lanesA, double* lanesB, double* gm,
             int64_t* isum) {
     auto* S = (sw_shard_state*)ctx;
@@ -3078,6 +3155,7 @@ int op_eval(void* ctx, int32_t sel, int32_t arg, double* lanesA, double* lanesB,
     }
     *gm = g;
     *isum = s;
+    if (sel == SW_EV_FINAL) SH_TRY(emit_enqueue(S, arg));
     return SW_OK;
 }
 
@@ -3475,7 +3553,8 @@ int prepare(sw_shard_state* S, const sw_problem* pr, int64_t off, int64_t N, boo
                S->R.reserve(NL) || S->p.reserve(NL) || S->jc.reserve(NL) || S->keys.reserve(NL * T) ||
                S->l.reserve(NL) || S->taken.reserve(NL) || S->tie.reserve(NL) ||
                S->tieblk.reserve(nblk((int64_t)NL)) ||
-               S->xa.reserve(2 * NL) || S->plan.reserve(NL * T) ||
+               S->xa.reserve(2 * NL) || (!dev && res->plan && S->plan.reserve(NL * T)) ||
+               (!dev && res->plan_masks && S->masks.reserve(NL)) ||
                S->planned.reserve(NL) || S->red.reserve((size_t)kRed * kRing) ||
                S->xrecv.reserve((xbytes / 8 + 1) * S->world) || S->pall.reserve(M) ||
                S->porder.reserve(M) || 
@@ -3520,8 +3599,11 @@ int prepare(sw_shard_state* S, const sw_problem* pr, int64_t off, int64_t N, boo
     v.tie = S->tie.p; v.tieblk = S->tieblk.p; v.xa = S->xa.p;
     for (int a = 0; a < SW_A_COUNT; ++a) v.arr[a] = S->arr[a].p;
     for (int a = 0; a < SW_Y_COUNT; ++a) v.y[a] = S->y[a].p;
-    v.plan = S->plan.p; v.planned = S->planned.p; v.red = S->red.p;
-    if (dev && res->plan) v.plan = res->plan; /* the final step writes the caller's HBM */
+    v.planned = S->planned.p; v.red = S->red.p;
+    /* the layouts this result asks for (k_emit_plan): the caller's HBM, or the
+     * engine's buffers for the copy back */
+    v.plan = dev ? res->plan : res->plan ? S->plan.p : nullptr;
+    v.masks = dev ? res->plan_masks : res->plan_masks ? S->masks.p : nullptr;
     if (dev && res->planned_rounds) v.planned = res->planned_rounds;
     S->ring_pos = kRing; /* the first step clears the ring */
     if (S->zero_pending) { /* the state, and the ring with it */
@@ -3561,7 +3643,7 @@ void sw_shard_release(sw_handle* h) {
     S->tie.release(); S->tieblk.release(); S->xa.release();
     S->planned.release(); S->porder.release(); S->d.release(); S->R.release();
     S->p.release(); S->xrecv.release(); S->jc.release(); S->keys.release();
-    S->plan.release(); S->red.release(); S->pall.release(); S->p2ws.release(); S->rrin.release(); S->rrrow.release(); S->rrws.release(); S->hx.release();
+    S->plan.release(); S->masks.release(); S->red.release(); S->pall.release(); S->p2ws.release(); S->rrin.release(); S->rrrow.release(); S->rrws.release(); S->hx.release();
     if (S->pub) (void)hipHostFree(S->pub);
     if (S->pub_flag) (void)hipHostFree(S->pub_flag);
     S->pub = nullptr; S->pub_flag = nullptr; S->pub_words = 0;
@@ -3933,6 +4015,7 @@ int fast_solve(sw_shard_state* S, const sw_problem* pr, int64_t N, sw_result* re
                (const unsigned long long*)srl, (const unsigned long long*)spf, W, LW,
                reinterpret_cast<FastOut*>(S->pub_dev), S->pub_flag_dev, seq, (const int*)S->xerr, Rdf,
                extra_iters, extra_status);
+        SH_TRY(emit_enqueue(S, SW_Y_CUR)); /* behind the result: it runs while the host wakes up */
         FAST_TRACE("final");
         /* one wait for the whole solve */
         auto t0 = std::chrono::steady_clock::now();
@@ -4024,6 +4107,8 @@ int dist_solve(sw_handle* h, const sw_problem* local, int64_t job_offset, int64_
     if (n && !dev) {
         if (res->plan)
             SH_HIP(S, hipMemcpyAsync(res->plan, S->plan.p, n * S->T, hipMemcpyDeviceToHost, h->stream));
+        if (res->plan_masks)
+            SH_HIP(S, hipMemcpyAsync(res->plan_masks, S->masks.p, n * 8, hipMemcpyDeviceToHost, h->stream));
         if (res->planned_rounds)
             SH_HIP(S, hipMemcpyAsync(res->planned_rounds, S->planned.p, n * 4, hipMemcpyDeviceToHost,
                                      h->stream));
@@ -4096,13 +4181,11 @@ extern "C" {
 
 int sw_dist_plan_solve(sw_handle* h, const sw_problem* local, int64_t job_offset, int64_t total_jobs,
                        sw_result* res) {
-    if (h && res && res->plan_masks) return h->err = "plan_masks: batch entry points only", SW_ERR_INVALID;
     return dist_solve(h, local, job_offset, total_jobs, res, false);
 }
 
 int sw_dist_plan_solve_dev(sw_handle* h, const sw_problem* local, int64_t job_offset,
                            int64_t total_jobs, sw_result* res) {
-    if (h && res && res->plan_masks) return h->err = "plan_masks: batch entry points only", SW_ERR_INVALID;
     return dist_solve(h, local, job_offset, total_jobs, res, true);
 }
 

@@ -265,9 +265,10 @@ class ProblemArrays:
 class DeviceShard:
     """One rank's jobs resident in HBM (torch tensors on `device`) for
     sw_dist_plan_solve_dev; plan [N, T] u8 and planned_rounds [N] i32 are
-    device tensors the solve writes."""
+    device tensors the solve writes, and with masks=True so is masks [N]: the
+    plan_masks words as int64 bit patterns."""
 
-    def __init__(self, arrays: ProblemArrays, device):
+    def __init__(self, arrays: ProblemArrays, device, masks: bool = False):
         import torch
         self.a = arrays
         dev = torch.device(device)
@@ -275,6 +276,7 @@ class DeviceShard:
             setattr(self, attr, torch.from_numpy(getattr(arrays, attr)).to(dev))
         self.plan = torch.zeros((arrays.N, arrays.T), dtype=torch.uint8, device=dev)
         self.planned = torch.zeros(arrays.N, dtype=torch.int32, device=dev)
+        self.masks = torch.zeros(arrays.N, dtype=torch.int64, device=dev) if masks else None
         torch.cuda.synchronize(dev)  # the handle's stream does not order after torch's
 
     def c_problem(self) -> SwProblem:
@@ -287,6 +289,8 @@ class DeviceShard:
         r = SwResult()
         r.plan = C.cast(C.c_void_p(self.plan.data_ptr()), _up)
         r.planned_rounds = C.cast(C.c_void_p(self.planned.data_ptr()), _ip)
+        if self.masks is not None:
+            r.plan_masks = C.cast(C.c_void_p(self.masks.data_ptr()), _mp)
         return r
 
 
@@ -928,21 +932,36 @@ class Solver:
         dist_init_host, on every rank."""
         self._check(self.lib.sw_dist_enable_peer(self.h, int(max_total_jobs)), "sw_dist_enable_peer")
 
-    def dist_solve(self, local: ProblemArrays, job_offset: int, total_jobs: int) -> dict:
+    def dist_solve(self, local: ProblemArrays, job_offset: int, total_jobs: int,
+                   masks: bool = False, plan: bool = True) -> dict:
+        """sw_dist_plan_solve on this rank's slice.  masks / plan as in
+        solve_batch: the bit-packed plan of the slice's jobs as "plan_masks",
+        and the byte plan left out (local.plan is not written)."""
         prob = local.c_problem()
         res = local.c_result()
+        if not plan:
+            res.plan = None
+        m = np.zeros(local.N, dtype=np.uint64) if masks else None
+        res.plan_masks = _ptr(m)
         rc = self.lib.sw_dist_plan_solve(self.h, C.byref(prob), int(job_offset), int(total_jobs),
                                          C.byref(res))
         comm = getattr(self, "_comm", None)
         if rc < 0 and comm is not None and comm.error is not None:
             raise NativeError(f"sw_dist_plan_solve: collective failed: {comm.error!r}")
         self._check(rc, "sw_dist_plan_solve")
-        return result_dict(res, local, rc)
+        d = result_dict(res, local, rc)
+        if masks:
+            d["plan_masks"] = m
+        return d
 
-    def dist_solve_dev(self, shard: "DeviceShard", job_offset: int, total_jobs: int) -> dict:
+    def dist_solve_dev(self, shard: "DeviceShard", job_offset: int, total_jobs: int,
+                       plan: bool = True) -> dict:
         """sw_dist_plan_solve_dev: inputs and the plan stay in HBM (shard's
-        tensors); only the scalar results come back."""
+        tensors: its masks too when it has them; plan=False leaves shard.plan
+        unwritten); only the scalar results come back."""
         prob, res = shard.c_problem(), shard.c_result()
+        if not plan:
+            res.plan = None
         rc = self.lib.sw_dist_plan_solve_dev(self.h, C.byref(prob), int(job_offset),
                                              int(total_jobs), C.byref(res))
         self._check(rc, "sw_dist_plan_solve_dev")
